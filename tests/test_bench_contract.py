@@ -74,6 +74,47 @@ def test_self_launch_gpus8_dry():
     assert d["config"]["parallelism"] == "async-dp8"
 
 
+def test_dump_outputs_and_full(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's results as float32
+    .npy files (well under 64 MB in all); with the same arguments the inputs,
+    and on the CPU's fp32 path therefore the outputs, repeat from run to run
+    (pinned to --device cpu: the bf16 GPU path does not repeat bit for bit).
+    `--full` is accepted and leaves the result line's schema alone."""
+    import numpy as np
+    runs = []
+    for sub, extra in (("a", ()), ("b", ("--full",))):
+        out = tmp_path / sub
+        d = run_bench("--device", "cpu", "--dump-outputs", str(out), *extra)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["loss.npy", "params.npy"]
+        arrs = {p.stem: np.load(p) for p in out.iterdir()}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        for name, a in arrs.items():
+            assert a.dtype == np.float32, name
+            assert np.isfinite(a).all(), name
+        assert arrs["loss"].shape == (1,)
+        assert abs(float(arrs["loss"][0]) - d["config"]["loss"]) < 1e-3
+        assert arrs["params"].shape == (d["config"]["n_params"],)
+        assert np.abs(arrs["params"]).max() > 0
+        runs.append(arrs)
+    for name in runs[0]:
+        np.testing.assert_allclose(runs[0][name], runs[1][name],
+                                   rtol=1e-4, atol=1e-6, err_msg=name)
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """An output over 2M elements is dumped as a fixed 2M-element sample."""
+    import numpy as np
+    n = (1 << 21) + 12345
+    run_bench("--mode", "paramsync", "--numel", str(n), "--interval", "0.001",
+              "--dump-outputs", str(tmp_path))
+    assert [p.name for p in tmp_path.iterdir()] == ["values.npy"]
+    v = np.load(tmp_path / "values.npy")
+    assert v.dtype == np.float32 and v.shape == (1 << 21,)
+    assert np.isfinite(v).all() and np.abs(v).max() > 0
+
+
 def test_paramsync_contract():
     d = run_bench("--mode", "paramsync", "--numel", "4096",
                   "--interval", "0.001")
