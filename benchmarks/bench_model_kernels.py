@@ -54,6 +54,54 @@ def main():
     out["torch_ln_bwd_ms"] = round(t(lambda: torch.autograd.grad(
         yt, (xt, wt, bt), dy, retain_graph=True)), 3)
 
+    # ---- fused add + LN vs the unfused sequence it replaces ----
+    # effective TB/s = mandatory bytes / time, with A = one (R, C) bf16
+    # activation: both forward and backward must move 4A
+    A = R * C * 2
+    delta = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+    dres = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+    x_new = torch.empty_like(x)
+    sums = torch.empty(3, C, dtype=torch.bfloat16, device="cuda")
+    part = torch.empty(_core.add_ln_max_blocks() * 3 * C,
+                       dtype=torch.float32, device="cuda")
+    ms = t(lambda: _core.add_ln_fwd(
+        x.data_ptr(), delta.data_ptr(), 0, w.data_ptr(), b.data_ptr(),
+        x_new.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+        R, C, 1e-5, s))
+    out["add_ln_fwd_ms"] = round(ms, 3)
+    out["add_ln_fwd_tbps"] = round(4 * A / ms / 1e9, 2)
+    ms = t(lambda: _core.add_ln_bwd(
+        dy.data_ptr(), x_new.data_ptr(), w.data_ptr(), mean.data_ptr(),
+        rstd.data_ptr(), dres.data_ptr(), dx.data_ptr(), sums[0].data_ptr(),
+        sums[1].data_ptr(), 0, part.data_ptr(), R, C, s))
+    out["add_ln_bwd_ms"] = round(ms, 3)
+    out["add_ln_bwd_tbps"] = round(4 * A / ms / 1e9, 2)
+    ms = t(lambda: _core.add_ln_bwd(
+        dy.data_ptr(), x_new.data_ptr(), w.data_ptr(), mean.data_ptr(),
+        rstd.data_ptr(), dres.data_ptr(), dx.data_ptr(), sums[0].data_ptr(),
+        sums[1].data_ptr(), sums[2].data_ptr(), part.data_ptr(), R, C, s))
+    out["add_ln_bwd_ddbias_ms"] = round(ms, 3)
+
+    def unfused_fwd():
+        torch.add(x, delta, out=x_new)
+        _core.ln_fwd(x_new.data_ptr(), w.data_ptr(), b.data_ptr(),
+                     y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, C,
+                     1e-5, s)
+
+    def unfused_bwd():
+        dwdb.zero_()
+        _core.ln_bwd(dy.data_ptr(), x_new.data_ptr(), w.data_ptr(),
+                     mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                     dwdb.data_ptr(), dwdb[C:].data_ptr(), R, C, s)
+        torch.add(dx, dres, out=y)
+        dwdb.to(torch.bfloat16)
+    ms = t(unfused_fwd)
+    out["unfused_add_ln_fwd_ms"] = round(ms, 3)
+    out["unfused_add_ln_fwd_tbps"] = round(4 * A / ms / 1e9, 2)
+    ms = t(unfused_bwd)
+    out["unfused_add_ln_bwd_ms"] = round(ms, 3)
+    out["unfused_add_ln_bwd_tbps"] = round(4 * A / ms / 1e9, 2)
+
     # ---- GELU (65536 x 3072) ----
     xg = torch.randn(65536, 3072, device="cuda").to(torch.bfloat16)
     yg = torch.empty_like(xg)

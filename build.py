@@ -26,6 +26,7 @@ SOURCES = [
     "rccl_transport.cpp",
     "hip_kernels.hip",
     "ln_kernels.hip",
+    "add_ln_kernels.hip",
     "ce_kernels.hip",
     "gelu_kernels.hip",
     "swiglu_kernels.hip",

@@ -180,11 +180,14 @@ void cpu_quantize(Codec c, float* delta, int64_t n, float scale, uint8_t* payloa
       });
       break;
     case Codec::Fp8: {
+      // a scale below 2^-127 (residuals near FLT_MIN) has no finite fp32
+      // reciprocal: v * inf would clamp everything to +-max, so divide there
       float inv = 1.0f / scale;
+      const bool div = !std::isfinite(inv);
       cpu_pfor(n, [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
           float v = atomic_load_f32(delta + i);
-          float sc = v * inv;
+          float sc = div ? v / scale : v * inv;
           sc = sc > 448.f ? 448.f : (sc < -448.f ? -448.f : sc);
           uint8_t q = f32_to_e4m3(sc);
           payload[i] = q;
@@ -195,10 +198,12 @@ void cpu_quantize(Codec c, float* delta, int64_t n, float scale, uint8_t* payloa
     }
     case Codec::Int4: {
       float inv = 1.0f / scale;
+      const bool div = !std::isfinite(inv);  // as for fp8
       cpu_pfor(n, [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
           float v = atomic_load_f32(delta + i);
-          float r = std::nearbyintf(v * inv);  // round-to-nearest-even
+          // round-to-nearest-even
+          float r = std::nearbyintf(div ? v / scale : v * inv);
           r = r > 7.f ? 7.f : (r < -7.f ? -7.f : r);
           int8_t q = static_cast<int8_t>(r);
           payload[i / 2] |= static_cast<uint8_t>(q & 0xF) << ((i % 2) * 4);

@@ -107,6 +107,27 @@ void hip_ln_bwd(const void* dy, const void* x, const void* w,
                 const float* mean, const float* rstd, void* dx, float* dgamma,
                 float* dbeta, int64_t R, int C, hipStream_t s);
 
+// Fused residual add + bf16 LayerNorm (add_ln_kernels.hip), wave per row,
+// for C a multiple of 256 up to 1024 (hip_add_ln_supported).  All tensor
+// pointers are bf16 and 8-byte aligned; mean/rstd/partial are fp32.
+//   fwd: x_new = bf16(x + delta [+ dbias]); y = LN(x_new).  delta == null
+//        means plain LN of x (x_new is not written, dbias must be null).
+//   bwd: dx_total = LN_dx(dy) + d_x_new (null: no residual gradient), one
+//        rounding; dgamma/dbeta/ddbias (null: not wanted) are written as
+//        bf16 by a second kernel from per-block partials — no atomics.
+//        `partial` holds hip_add_ln_max_blocks() * 3 * C floats, 16-byte
+//        aligned, and needs no zeroing.
+bool hip_add_ln_supported(int C);
+int hip_add_ln_max_blocks();
+void hip_add_ln_fwd(const void* x, const void* delta, const void* dbias,
+                    const void* w, const void* b, void* x_new, void* y,
+                    float* mean, float* rstd, int64_t R, int C, float eps,
+                    hipStream_t s);
+void hip_add_ln_bwd(const void* dy, const void* x_new, const void* w,
+                    const float* mean, const float* rstd, const void* d_x_new,
+                    void* dx_total, void* dgamma, void* dbeta, void* ddbias,
+                    float* partial, int64_t R, int C, hipStream_t s);
+
 // Column sum of (R, C) bf16 into fp32 out[C] (Linear backward bias grad);
 // caller zeroes `out` first.
 void hip_colsum_bf16(const void* x, float* out, int64_t R, int C,

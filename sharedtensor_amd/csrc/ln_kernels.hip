@@ -11,6 +11,11 @@
 //
 // Shapes: x is (R, C) row-major bf16, C <= 4096 (the wrapper falls back to
 // torch otherwise), weights/bias bf16[C].
+//
+// For C a multiple of 256 up to 1024 (GPT-2-small's 768) the training path
+// now runs the wave-per-row kernels in add_ln_kernels.hip, which also fold
+// the residual add and the dgamma/dbeta sums into one pass each way; the
+// LayerNorm kernels here serve every other width.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
