@@ -194,6 +194,17 @@ def main():
     out["ce_bwd_ms"] = round(t(lambda: _core.ce_bwd(
         logits.data_ptr(), targets32.data_ptr(), row_lse.data_ptr(),
         dlog.data_ptr(), g.data_ptr(), 1.0 / R, R, V, s), iters=5), 3)
+    # one-pass loss + dlogits: mandatory bytes = one read + one write of the
+    # logits; compare with ce_fwd_ms + ce_bwd_ms (three reads + one write)
+    ms = t(lambda: _core.ce_fwd_grad(
+        logits.data_ptr(), targets32.data_ptr(), loss.data_ptr(),
+        row_lse.data_ptr(), dlog.data_ptr(), 1.0 / R, R, V, s), iters=5)
+    out["ce_fwd_grad_ms"] = round(ms, 3)
+    out["ce_fwd_grad_tbps"] = round(2 * logits.numel() * 2 / ms / 1e9, 2)
+    out["ce_bwd_skip_unit_ms"] = round(t(lambda: _core.ce_bwd(
+        logits.data_ptr(), targets32.data_ptr(), row_lse.data_ptr(),
+        dlog.data_ptr(), g.data_ptr(), 1.0 / R, R, V, s,
+        skip_if_unit=True), iters=5), 4)
     lt = logits.clone().requires_grad_(True)
     out["torch_ce_fwd_ms"] = round(t(lambda: torch.nn.functional.cross_entropy(
         lt, targets), iters=5), 3)

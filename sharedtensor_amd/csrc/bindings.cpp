@@ -255,15 +255,31 @@ PYBIND11_MODULE(_core, m) {
   });
   m.def("ce_bwd", [](uintptr_t logits, uintptr_t targets, uintptr_t row_lse,
                      uintptr_t dlogits, uintptr_t gscale_dev, double inv_r,
-                     int64_t R, int64_t V, uintptr_t stream) {
+                     int64_t R, int64_t V, uintptr_t stream,
+                     bool skip_if_unit) {
     hip_ce_bwd(reinterpret_cast<const void*>(logits),
                reinterpret_cast<const int32_t*>(targets),
                reinterpret_cast<const float*>(row_lse),
                reinterpret_cast<void*>(dlogits),
                reinterpret_cast<const float*>(gscale_dev),
-               static_cast<float>(inv_r), R, V,
+               static_cast<float>(inv_r), R, V, skip_if_unit,
                reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("logits"), py::arg("targets"), py::arg("row_lse"),
+     py::arg("dlogits"), py::arg("gscale_dev"), py::arg("inv_r"),
+     py::arg("R"), py::arg("V"), py::arg("stream"),
+     py::arg("skip_if_unit") = false);
+  m.def("ce_fwd_grad", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,
+                          uintptr_t row_lse, uintptr_t dlogits, double inv_r,
+                          int64_t R, int64_t V, uintptr_t stream) {
+    hip_ce_fwd_grad(reinterpret_cast<const void*>(logits),
+                    reinterpret_cast<const int32_t*>(targets),
+                    reinterpret_cast<float*>(loss),
+                    reinterpret_cast<float*>(row_lse),
+                    reinterpret_cast<void*>(dlogits),
+                    static_cast<float>(inv_r), R, V,
+                    reinterpret_cast<hipStream_t>(stream));
   });
+  m.def("ce_fwd_grad_max_v", &hip_ce_fwd_grad_max_v);
 
   // fused bf16 LayerNorm (pointers are bf16 unless named mean/rstd/dgamma/
   // dbeta, which are fp32)

@@ -142,14 +142,23 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
                  const float* rstd, void* dx, float* dgamma, int64_t R, int C,
                  hipStream_t s);
 
-// Fused bf16 cross-entropy (ce_kernels.hip): online-logsumexp fwd saving
-// per-row (max, lse); bwd writes bf16 dlogits = g*(softmax - onehot).
+// Fused bf16 cross-entropy (ce_kernels.hip): two-pass stats-only fwd saving
+// per-row (max, lse); bwd writes bf16 dlogits = g*(softmax - onehot), or in
+// skip_if_unit mode leaves the buffer alone when *gscale_dev == 1.
 void hip_ce_fwd(const void* logits, const int32_t* targets, float* loss,
                 float* row_m, float* row_lse, int64_t R, int64_t V,
                 hipStream_t s);
 void hip_ce_bwd(const void* logits, const int32_t* targets,
                 const float* row_lse, void* dlogits, const float* gscale_dev,
-                float inv_r, int64_t R, int64_t V, hipStream_t s);
+                float inv_r, int64_t R, int64_t V, bool skip_if_unit,
+                hipStream_t s);
+// One-pass fwd + grad: one read of the logits gives loss, row_lse and the
+// bf16 dlogits for an upstream gradient of 1 (inv_r = 1/R).  Throws when
+// V > hip_ce_fwd_grad_max_v() (the row must fit one block's registers).
+int64_t hip_ce_fwd_grad_max_v();
+void hip_ce_fwd_grad(const void* logits, const int32_t* targets, float* loss,
+                     float* row_lse, void* dlogits, float inv_r, int64_t R,
+                     int64_t V, hipStream_t s);
 
 // Fused bf16 SwiGLU (swiglu_kernels.hip): y = silu(x1)*x3 one kernel each
 // way; n must be a multiple of 8, buffers 16-byte aligned (uint4 loads).
