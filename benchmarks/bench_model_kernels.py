@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Microbenchmark the model-side fused kernels (LN, CE) vs torch equivalents
-on the GPT-2-small B=64 shapes."""
+"""Microbenchmark the model-side fused kernels (LN, add+LN, GELU, RMSNorm,
+colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the GPT-2-small B=64
+and llama-1B bench shapes.  `--only-rope` runs the RoPE section alone."""
 import json
 import sys
 import time
@@ -22,10 +23,48 @@ def t(fn, iters=10, warmup=3):
     return (time.perf_counter() - t0) / iters * 1e3  # ms
 
 
+def bench_rope(out):
+    # ---- RoPE (llama-1B shape: B*T=16384, T=4096, 32 q + 8 kv heads, D=64)
+    # fused q+k launch vs eager apply_rope on q and on k; effective TB/s
+    # from the mandatory bytes: one read + one write of q and k per direction
+    from sharedtensor_amd.models.llama import apply_rope, rope_freqs
+    from sharedtensor_amd.ops import fused_rope
+    Bq, Tq, Hq, Hkv, Dq = 4, 4096, 32, 8, 64
+    rq = torch.randn(Bq, Tq, Hq, Dq, device="cuda").to(
+        torch.bfloat16).transpose(1, 2).requires_grad_(True)
+    rk = torch.randn(Bq, Tq, Hkv, Dq, device="cuda").to(
+        torch.bfloat16).transpose(1, 2).requires_grad_(True)
+    rgq = torch.randn(Bq, Hq, Tq, Dq, device="cuda").to(torch.bfloat16)
+    rgk = torch.randn(Bq, Hkv, Tq, Dq, device="cuda").to(torch.bfloat16)
+    rcos, rsin = rope_freqs(Dq, Tq, 500000.0, "cuda")
+    assert fused_rope.can_use(rq, rk, rcos, rsin)
+    rope_bytes = 2 * (rq.numel() + rk.numel()) * 2
+    with torch.no_grad():
+        ms = t(lambda: fused_rope.fused_rope_qk(rq, rk, rcos, rsin), iters=50)
+    out["rope_fwd_ms"] = round(ms, 4)
+    out["rope_fwd_tbps"] = round(rope_bytes / ms / 1e9, 2)
+    ry = fused_rope.fused_rope_qk(rq, rk, rcos, rsin)
+    ms = t(lambda: torch.autograd.grad(ry, (rq, rk), (rgq, rgk),
+                                       retain_graph=True), iters=50)
+    out["rope_bwd_ms"] = round(ms, 4)
+    out["rope_bwd_tbps"] = round(rope_bytes / ms / 1e9, 2)
+    with torch.no_grad():
+        out["torch_rope_fwd_ms"] = round(t(lambda: (
+            apply_rope(rq, rcos, rsin), apply_rope(rk, rcos, rsin)),
+            iters=50), 4)
+    ryt = (apply_rope(rq, rcos, rsin), apply_rope(rk, rcos, rsin))
+    out["torch_rope_bwd_ms"] = round(t(lambda: torch.autograd.grad(
+        ryt, (rq, rk), (rgq, rgk), retain_graph=True), iters=50), 4)
+
+
 def main():
     torch.cuda.set_device(0)
     s = torch.cuda.current_stream().cuda_stream
     out = {}
+    if "--only-rope" in sys.argv[1:]:
+        bench_rope(out)
+        print(json.dumps(out, indent=1))
+        return
 
     # ---- LN (R=65536, C=768) ----
     R, C = 65536, 768
@@ -177,6 +216,8 @@ def main():
     syt = torch.nn.functional.silu(sa) * sb
     out["torch_swiglu_bwd_ms"] = round(t(lambda: torch.autograd.grad(
         syt, (sa, sb), sdy, retain_graph=True)), 3)
+
+    bench_rope(out)
 
     # ---- CE (R=65536, V=50257) ----
     R, V = 65536, 50257

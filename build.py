@@ -30,6 +30,7 @@ SOURCES = [
     "ce_kernels.hip",
     "gelu_kernels.hip",
     "swiglu_kernels.hip",
+    "rope_kernels.hip",
     "bindings.cpp",
 ]
 

@@ -7,6 +7,8 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
+
 #include "codec_cpu.h"
 #include "engine.h"
 #include "rccl_transport.h"
@@ -316,6 +318,33 @@ PYBIND11_MODULE(_core, m) {
                    reinterpret_cast<void*>(dx3), n,
                    reinterpret_cast<hipStream_t>(stream));
   });
+  // fused RoPE over q and k; strides are (B, H, T) element strides, k == 0
+  // rotates q alone
+  m.def("rope_qk", [](uintptr_t q, uintptr_t k, uintptr_t q_out,
+                      uintptr_t k_out, uintptr_t cos, uintptr_t sin,
+                      int64_t B, int64_t Hq, int64_t Hkv, int64_t T,
+                      int64_t D, std::array<int64_t, 3> q_strides,
+                      std::array<int64_t, 3> k_strides,
+                      std::array<int64_t, 3> q_out_strides,
+                      std::array<int64_t, 3> k_out_strides, bool inverse,
+                      uintptr_t stream) {
+    auto st = [](const std::array<int64_t, 3>& a) {
+      return RopeStrides{a[0], a[1], a[2]};
+    };
+    hip_rope_qk(reinterpret_cast<const void*>(q),
+                reinterpret_cast<const void*>(k),
+                reinterpret_cast<void*>(q_out),
+                reinterpret_cast<void*>(k_out),
+                reinterpret_cast<const float*>(cos),
+                reinterpret_cast<const float*>(sin), B, Hq, Hkv, T, D,
+                st(q_strides), st(k_strides), st(q_out_strides),
+                st(k_out_strides), inverse,
+                reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("q"), py::arg("k"), py::arg("q_out"), py::arg("k_out"),
+     py::arg("cos"), py::arg("sin"), py::arg("B"), py::arg("Hq"),
+     py::arg("Hkv"), py::arg("T"), py::arg("D"), py::arg("q_strides"),
+     py::arg("k_strides"), py::arg("q_out_strides"),
+     py::arg("k_out_strides"), py::arg("inverse"), py::arg("stream"));
   m.def("rms_fwd", [](uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t rstd,
                       int64_t R, int C, double eps, uintptr_t stream) {
     hip_rms_fwd(reinterpret_cast<const void*>(x),

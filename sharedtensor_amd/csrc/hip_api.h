@@ -167,6 +167,22 @@ void hip_swiglu_fwd(const void* x1, const void* x3, void* y, int64_t n,
 void hip_swiglu_bwd(const void* dy, const void* x1, const void* x3, void* dx1,
                     void* dx3, int64_t n, hipStream_t s);
 
+// Fused bf16 RoPE for q and k in one launch (rope_kernels.hip).  q is
+// logically (B, Hq, T, D) and k (B, Hkv, T, D), each side addressed by
+// element strides for B, H, T with D contiguous; cos/sin are fp32 (>=T, D/2)
+// row-major.  Pairs (2i, 2i+1) rotate by the angle at (t, i); `inverse`
+// rotates by the negated angle (the gradient).  k == null rotates q alone.
+// Throws on odd D or a null q/q_out/cos/sin.  16-byte accesses when D % 8
+// == 0 and all bases/strides keep 16-byte alignment, pairs otherwise.
+struct RopeStrides {
+  int64_t b = 0, h = 0, t = 0;
+};
+void hip_rope_qk(const void* q, const void* k, void* q_out, void* k_out,
+                 const float* cos, const float* sin, int64_t B, int64_t Hq,
+                 int64_t Hkv, int64_t T, int64_t D, const RopeStrides& q_in,
+                 const RopeStrides& k_in, const RopeStrides& q_os,
+                 const RopeStrides& k_os, bool inverse, hipStream_t s);
+
 // Fused bf16 GELU-tanh (gelu_kernels.hip); n must be even, buffers
 // 4-byte aligned (pair loads).
 void hip_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s);

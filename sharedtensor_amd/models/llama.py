@@ -97,8 +97,17 @@ class LlamaAttention(nn.Module):
         q = self.wq(x).view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = self.wk(x).view(B, T, self.n_kv, self.head_dim).transpose(1, 2)
         v = self.wv(x).view(B, T, self.n_kv, self.head_dim).transpose(1, 2)
-        q = apply_rope(q, cos, sin)
-        k = apply_rope(k, cos, sin)
+        fused = False
+        if q.is_cuda and q.dtype == torch.bfloat16:
+            # one fused CDNA4 launch rotates q and k (csrc/rope_kernels.hip),
+            # bit-identical to the two apply_rope chains it replaces
+            from ..ops import fused_rope
+            fused = fused_rope.can_use(q, k, cos, sin)
+            if fused:
+                q, k = fused_rope.fused_rope_qk(q, k, cos, sin)
+        if not fused:
+            q = apply_rope(q, cos, sin)
+            k = apply_rope(k, cos, sin)
         if x.is_cuda:
             # same backend priority as GPT-2 (+16% measured; MATH fallback
             # covers shapes a backend rejects, e.g. GQA corner cases)
