@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Microbenchmark the model-side fused kernels (LN, add+LN, GELU, RMSNorm,
-colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the GPT-2-small B=64
-and llama-1B bench shapes.  `--only-rope` runs the RoPE section alone."""
+add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
+GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
+section alone, `--only-add-rms` the add+RMSNorm section."""
 import json
 import sys
 import time
@@ -57,12 +58,71 @@ def bench_rope(out):
         ryt, (rq, rk), (rgq, rgk), retain_graph=True), iters=50), 4)
 
 
+def bench_add_rms(out):
+    # ---- fused add + RMSNorm vs the unfused sequence it replaces (llama-1B
+    # C=2048 and llama-8B C=4096, R=16384).  effective TB/s = mandatory
+    # bytes / time, with A = one (R, C) bf16 activation: forward must move
+    # 4A (x, delta in; x_new, y out), backward 4A (dy, x_new, d_x_new in;
+    # dx out).  Of the 8 the fused pair moves, 3 + 5 are reads and writes
+    # the unfused sequence also pays for; it moves 13.
+    s = torch.cuda.current_stream().cuda_stream
+    R = 16384
+    for C in (2048, 4096):
+        A = R * C * 2
+        x = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+        delta = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+        w = torch.randn(C, device="cuda").to(torch.bfloat16)
+        dy = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+        dres = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+        x_new, y, dx = (torch.empty_like(x) for _ in range(3))
+        dx2 = torch.empty_like(x)
+        rstd = torch.empty(R, dtype=torch.float32, device="cuda")
+        dg = torch.empty(C, dtype=torch.bfloat16, device="cuda")
+        dg32 = torch.zeros(C, dtype=torch.float32, device="cuda")
+        part = torch.empty(_core.add_rms_max_blocks() * C,
+                           dtype=torch.float32, device="cuda")
+        ms = t(lambda: _core.add_rms_fwd(
+            x.data_ptr(), delta.data_ptr(), w.data_ptr(), x_new.data_ptr(),
+            y.data_ptr(), rstd.data_ptr(), R, C, 1e-5, s), iters=30)
+        out[f"add_rms{C}_fwd_ms"] = round(ms, 4)
+        out[f"add_rms{C}_fwd_tbps"] = round(4 * A / ms / 1e9, 2)
+        ms = t(lambda: _core.add_rms_bwd(
+            dy.data_ptr(), x_new.data_ptr(), w.data_ptr(), rstd.data_ptr(),
+            dres.data_ptr(), dx.data_ptr(), dg.data_ptr(), part.data_ptr(),
+            R, C, s), iters=30)
+        out[f"add_rms{C}_bwd_ms"] = round(ms, 4)
+        out[f"add_rms{C}_bwd_tbps"] = round(4 * A / ms / 1e9, 2)
+
+        def unfused_fwd():
+            torch.add(x, delta, out=x_new)
+            _core.rms_fwd(x_new.data_ptr(), w.data_ptr(), y.data_ptr(),
+                          rstd.data_ptr(), R, C, 1e-5, s)
+
+        def unfused_bwd():
+            dg32.zero_()
+            _core.rms_bwd(dy.data_ptr(), x_new.data_ptr(), w.data_ptr(),
+                          rstd.data_ptr(), dx.data_ptr(), dg32.data_ptr(),
+                          R, C, s)
+            torch.add(dx, dres, out=dx2)
+            dg32.to(torch.bfloat16)
+        ms = t(unfused_fwd, iters=30)
+        out[f"unfused_add_rms{C}_fwd_ms"] = round(ms, 4)
+        out[f"unfused_add_rms{C}_fwd_tbps"] = round(4 * A / ms / 1e9, 2)
+        ms = t(unfused_bwd, iters=30)
+        out[f"unfused_add_rms{C}_bwd_ms"] = round(ms, 4)
+        out[f"unfused_add_rms{C}_bwd_tbps"] = round(4 * A / ms / 1e9, 2)
+
+
 def main():
     torch.cuda.set_device(0)
     s = torch.cuda.current_stream().cuda_stream
     out = {}
     if "--only-rope" in sys.argv[1:]:
         bench_rope(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-add-rms" in sys.argv[1:]:
+        bench_add_rms(out)
         print(json.dumps(out, indent=1))
         return
 
@@ -218,6 +278,7 @@ def main():
         syt, (sa, sb), sdy, retain_graph=True)), 3)
 
     bench_rope(out)
+    bench_add_rms(out)
 
     # ---- CE (R=65536, V=50257) ----
     R, V = 65536, 50257

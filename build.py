@@ -27,6 +27,7 @@ SOURCES = [
     "hip_kernels.hip",
     "ln_kernels.hip",
     "add_ln_kernels.hip",
+    "add_rms_kernels.hip",
     "ce_kernels.hip",
     "gelu_kernels.hip",
     "swiglu_kernels.hip",

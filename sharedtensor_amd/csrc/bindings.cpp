@@ -412,6 +412,37 @@ PYBIND11_MODULE(_core, m) {
                    reinterpret_cast<hipStream_t>(stream));
   });
 
+  // fused residual add + RMSNorm; 0 for an absent optional pointer
+  m.def("add_rms_supported", &hip_add_rms_supported);
+  m.def("add_rms_max_blocks", &hip_add_rms_max_blocks);
+  m.def("add_rms_fwd", [](uintptr_t x, uintptr_t delta, uintptr_t w,
+                          uintptr_t x_new, uintptr_t y, uintptr_t rstd,
+                          int64_t R, int C, double eps, uintptr_t stream) {
+    hip_add_rms_fwd(reinterpret_cast<const void*>(x),
+                    reinterpret_cast<const void*>(delta),
+                    reinterpret_cast<const void*>(w),
+                    reinterpret_cast<void*>(x_new),
+                    reinterpret_cast<void*>(y),
+                    reinterpret_cast<float*>(rstd), R, C,
+                    static_cast<float>(eps),
+                    reinterpret_cast<hipStream_t>(stream));
+  });
+  m.def("add_rms_bwd", [](uintptr_t dy, uintptr_t x_new, uintptr_t w,
+                          uintptr_t rstd, uintptr_t d_x_new,
+                          uintptr_t dx_total, uintptr_t dgamma,
+                          uintptr_t partial, int64_t R, int C,
+                          uintptr_t stream) {
+    hip_add_rms_bwd(reinterpret_cast<const void*>(dy),
+                    reinterpret_cast<const void*>(x_new),
+                    reinterpret_cast<const void*>(w),
+                    reinterpret_cast<const float*>(rstd),
+                    reinterpret_cast<const void*>(d_x_new),
+                    reinterpret_cast<void*>(dx_total),
+                    reinterpret_cast<void*>(dgamma),
+                    reinterpret_cast<float*>(partial), R, C,
+                    reinterpret_cast<hipStream_t>(stream));
+  });
+
   m.def("msg_bytes", &Engine::msg_bytes);
   m.def("scales_area", &Engine::scales_area);
   m.def("payload_bytes",

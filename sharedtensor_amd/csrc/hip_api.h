@@ -142,6 +142,28 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
                  const float* rstd, void* dx, float* dgamma, int64_t R, int C,
                  hipStream_t s);
 
+// Fused residual add + bf16 RMSNorm (add_rms_kernels.hip), wave per row,
+// for C a multiple of 512 up to 4096 (hip_add_rms_supported).  All tensor
+// pointers are bf16 and 16-byte aligned; rstd/partial are fp32.  Both
+// throw on an unsupported C or a misaligned pointer.
+//   fwd: x_new = bf16(x + delta); y = x_new * rstd * w from the rounded
+//        x_new.  delta == null means plain RMSNorm of x (x_new is not
+//        written); delta without x_new throws.  R == 0 launches nothing.
+//   bwd: dx_total = RMS_dx(dy) + d_x_new (null: no residual gradient), one
+//        rounding; dgamma is written as bf16 by a second kernel from
+//        per-block partials — no atomics, so it repeats bit for bit.
+//        `partial` holds hip_add_rms_max_blocks() * C floats and needs no
+//        zeroing.  R == 0 throws.
+bool hip_add_rms_supported(int C);
+int hip_add_rms_max_blocks();
+void hip_add_rms_fwd(const void* x, const void* delta, const void* w,
+                     void* x_new, void* y, float* rstd, int64_t R, int C,
+                     float eps, hipStream_t s);
+void hip_add_rms_bwd(const void* dy, const void* x_new, const void* w,
+                     const float* rstd, const void* d_x_new, void* dx_total,
+                     void* dgamma, float* partial, int64_t R, int C,
+                     hipStream_t s);
+
 // Fused bf16 cross-entropy (ce_kernels.hip): two-pass stats-only fwd saving
 // per-row (max, lse); bwd writes bf16 dlogits = g*(softmax - onehot), or in
 // skip_if_unit mode leaves the buffer alone when *gscale_dev == 1.

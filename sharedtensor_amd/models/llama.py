@@ -8,6 +8,7 @@ deltas = <=128 GB, comfortably inside 288 GB of HBM3E per GPU.
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 
 import torch
@@ -60,6 +61,28 @@ class RMSNorm(nn.Module):
         x = x.float()
         x = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + self.eps)
         return (x * self.weight.float()).to(dt)
+
+
+def add_rms(norm: RMSNorm, x, delta):
+    """``x = x + delta; h = norm(x)`` -> (x, h).
+
+    On the fused path the add rides inside the RMSNorm kernels, forward and
+    backward (ops/fused_rms.py).  Everywhere else — CPU, fp32, a width the
+    kernels do not cover, or SHTENS_NO_FUSED_ADD_RMS=1 — it is the plain
+    torch add followed by ``norm(x)``, value for value what
+    ``x = x + f(norm(x))`` computes.  ``delta=None`` is the first norm of the
+    model: nothing to add.
+    """
+    if delta is None:
+        return x, norm(x)
+    if x.is_cuda and x.dtype == torch.bfloat16 \
+            and norm.weight.dtype == torch.bfloat16:
+        from ..ops import fused_rms
+        if fused_rms.can_use_add(x, norm.weight):
+            return fused_rms.fused_add_rms_norm(x, delta, norm.weight,
+                                                norm.eps)
+    x = x + delta
+    return x, norm(x)
 
 
 def rope_freqs(head_dim, max_seq, theta, device):
@@ -152,10 +175,15 @@ class LlamaBlock(nn.Module):
         self.mlp_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.mlp = LlamaMLP(cfg)
 
-    def forward(self, x, cos, sin):
-        x = x + self.attn(self.attn_norm(x), cos, sin)
-        x = x + self.mlp(self.mlp_norm(x))
-        return x
+    def forward(self, x, cos, sin, delta=None):
+        """Takes the residual stream and the previous block's MLP output not
+        yet added to it; returns the same pair, so every residual add
+        happens inside the RMSNorm that follows it.  With ``delta=None``
+        this is ``x = x + attn(attn_norm(x))`` and the caller owes
+        ``x + m`` for the MLP."""
+        x, h = add_rms(self.attn_norm, x, delta)
+        x, h = add_rms(self.mlp_norm, x, self.attn(h, cos, sin))
+        return x, self.mlp(h)
 
 
 class Llama(nn.Module):
@@ -184,14 +212,24 @@ class Llama(nn.Module):
     def forward(self, idx, targets=None):
         x = self.tok(idx)
         cos, sin = self._rope_cache(idx.device, x.dtype)
+        delta = None
         for blk in self.blocks:
-            x = blk(x, cos, sin)
-        x = self.norm(x)
+            x, delta = blk(x, cos, sin, delta)
+        _, x = add_rms(self.norm, x, delta)  # absorbs the last add
         logits = self.lm_head(x)
         if targets is None:
             return logits, None
-        loss = F.cross_entropy(logits.float().view(-1, logits.size(-1)),
-                               targets.reshape(-1))
+        flat = logits.view(-1, logits.size(-1))
+        tgt = targets.reshape(-1)
+        if flat.is_cuda and flat.dtype == torch.bfloat16 \
+                and os.environ.get("SHTENS_NO_FUSED_CE_LLAMA") != "1":
+            # one read of the bf16 logits gives loss and dlogits
+            # (csrc/ce_kernels.hip) instead of an fp32 copy of the logits
+            # plus torch's fp32 log-softmax; the knob is for A/B runs
+            from ..ops import fused_ce
+            if fused_ce.can_use(flat):
+                return logits, fused_ce.fused_cross_entropy(flat, tgt)
+        loss = F.cross_entropy(flat.float(), tgt)
         return logits, loss
 
     def num_params(self):
