@@ -45,7 +45,14 @@ static __device__ __forceinline__ float gelu_f(float x) {
   return 0.5f * x * (1.f + tanhf(inner));
 }
 
-static __device__ __forceinline__ float gelu_grad_f(float x) {
+// gelu'(x) is 1 or 0 to well below fp32 resolution for |x| >= 10, so the
+// formula is evaluated at x clamped to [-10, 10]: unclamped, x * x reaches
+// inf for |x| > 1.8e19 and sech2 == 0 then meets it as 0 * inf = NaN.  NaN
+// passes through the clamp (fminf/fmaxf return the other operand, so the
+// NaN is put back by hand).
+static __device__ __forceinline__ float gelu_grad_f(float xin) {
+  float x = fminf(fmaxf(xin, -10.f), 10.f);
+  if (xin != xin) x = xin;
   float x2 = x * x;
   float inner = GK * x * (1.f + GC * x2);
   float t = tanhf(inner);
@@ -89,14 +96,27 @@ __global__ void k_gelu_bwd(const uint4* __restrict__ dy,
   }
 }
 
+// The kernels load and store uint4.  contiguous() keeps an offset view of a
+// larger buffer as it is, so the pointers are checked here; the Python
+// wrapper clones a tensor that fails this.
+static void gelu_check_align(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) & 15u)
+    throw std::runtime_error(std::string("gelu: ") + what +
+                             " is not 16-byte aligned");
+}
+
 static inline int gelu_grid(int64_t npairs) {
   int64_t g = (npairs + 255) / 256;
   return static_cast<int>(g < 16384 ? (g > 0 ? g : 1) : 16384);
 }
 
 void hip_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s) {
-  // wrapper guarantees n % 8 == 0 and 16-byte alignment
+  // the wrapper arranges n % 8 == 0 and 16-byte alignment; both are
+  // checked here because nothing else guarantees them
   if (n % 8) throw std::runtime_error("gelu: n must be a multiple of 8");
+  gelu_check_align(x, "x");
+  gelu_check_align(y, "y");
+  if (n <= 0) return;
   hipLaunchKernelGGL(k_gelu_fwd, dim3(gelu_grid(n / 8)), dim3(256), 0, s,
                      static_cast<const uint4*>(x),
                      static_cast<uint4*>(y), n / 8);
@@ -106,6 +126,10 @@ void hip_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s) {
 void hip_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n,
                   hipStream_t s) {
   if (n % 8) throw std::runtime_error("gelu: n must be a multiple of 8");
+  gelu_check_align(dy, "dy");
+  gelu_check_align(x, "x");
+  gelu_check_align(dx, "dx");
+  if (n <= 0) return;
   hipLaunchKernelGGL(k_gelu_bwd, dim3(gelu_grid(n / 8)), dim3(256), 0, s,
                      static_cast<const uint4*>(dy),
                      static_cast<const uint4*>(x),

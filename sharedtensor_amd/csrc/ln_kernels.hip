@@ -57,6 +57,16 @@ static __device__ __forceinline__ uint32_t bf16pair_pack(float lo, float hi) {
 
 constexpr int LN_BLOCK = 256;  // 4 waves
 
+// The fwd and dx kernels load and store bf16 pairs as uint32.  contiguous()
+// keeps an offset view of a larger buffer as it is, so the callers' pointers
+// are checked here, before any launch.  (The dw/db and colsum kernels load
+// scalars and take any bf16 pointer.)
+static void ln_check_align(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) & 3u)
+    throw std::runtime_error(std::string("ln/rms: ") + what +
+                             " is not 4-byte aligned");
+}
+
 // Block-wide sum of one value per thread (4-wave block): wave shfl tree +
 // LDS combine.  Returns the total to every thread.
 static __device__ __forceinline__ float block_sum(float v, float* lds4) {
@@ -88,7 +98,7 @@ __global__ void k_ln_fwd(const uint16_t* __restrict__ x,
   const uint32_t* bp = reinterpret_cast<const uint32_t*>(b);
   uint32_t* yr = reinterpret_cast<uint32_t*>(y + r * C);
   float x0[CPT], x1[CPT];
-  float s = 0.f, ss = 0.f;
+  float s = 0.f;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     int c = threadIdx.x + k * LN_BLOCK;
@@ -101,13 +111,21 @@ __global__ void k_ln_fwd(const uint16_t* __restrict__ x,
     x0[k] = a;
     x1[k] = bb;
     s += a + bb;
-    ss += a * a + bb * bb;
   }
-  float tot = block_sum(s, lds4);
-  float tot2 = block_sum(ss, lds4);
-  float m = tot / C;
-  float var = tot2 / C - m * m;
-  float rs = rsqrtf(var > 0.f ? var + eps : eps);
+  float m = block_sum(s, lds4) / C;
+  // two-pass variance from the cached row: sum((x - m)^2) does not cancel
+  // the way sum(x^2)/C - m^2 does when |mean| >> std.  Columns past the row
+  // hold 0 in the cache and must add 0 here, not m^2.
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    int c = threadIdx.x + k * LN_BLOCK;
+    if (c < C2) {
+      float d0 = x0[k] - m, d1 = x1[k] - m;
+      ss += d0 * d0 + d1 * d1;
+    }
+  }
+  float rs = rsqrtf(block_sum(ss, lds4) / C + eps);
   if (threadIdx.x == 0) {
     mean[r] = m;
     rstd[r] = rs;
@@ -335,6 +353,10 @@ __global__ void k_rms_bwd_dw(const uint16_t* __restrict__ dy,
 void hip_rms_fwd(const void* x, const void* w, void* y, float* rstd,
                  int64_t R, int C, float eps, hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("rms: bad C");
+  ln_check_align(x, "x");
+  ln_check_align(w, "weight");
+  ln_check_align(y, "y");
+  if (R <= 0) return;  // a grid of 0 blocks is an invalid configuration
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(R)), dim3(LN_BLOCK), 0,
@@ -346,8 +368,7 @@ void hip_rms_fwd(const void* x, const void* w, void* y, float* rstd,
   else if (cpt <= 2) launch(k_rms_fwd<2>);
   else if (cpt <= 3) launch(k_rms_fwd<3>);
   else if (cpt <= 4) launch(k_rms_fwd<4>);
-  else if (cpt <= 8) launch(k_rms_fwd<8>);
-  else launch(k_rms_fwd<16>);
+  else launch(k_rms_fwd<8>);  // C <= LN_MAXC: cpt <= 8
   HIP_CHECK_LN(hipGetLastError());
 }
 
@@ -355,6 +376,11 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
                  const float* rstd, void* dx, float* dgamma, int64_t R, int C,
                  hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("rms: bad C");
+  ln_check_align(dy, "dy");
+  ln_check_align(x, "x");
+  ln_check_align(w, "weight");
+  ln_check_align(dx, "dx");
+  if (R <= 0) return;  // dgamma stays as the caller zeroed it
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch_dx = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(R)), dim3(LN_BLOCK), 0,
@@ -367,8 +393,7 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
   else if (cpt <= 2) launch_dx(k_rms_bwd_dx<2>);
   else if (cpt <= 3) launch_dx(k_rms_bwd_dx<3>);
   else if (cpt <= 4) launch_dx(k_rms_bwd_dx<4>);
-  else if (cpt <= 8) launch_dx(k_rms_bwd_dx<8>);
-  else launch_dx(k_rms_bwd_dx<16>);
+  else launch_dx(k_rms_bwd_dx<8>);  // C <= LN_MAXC: cpt <= 8
   HIP_CHECK_LN(hipGetLastError());
   int g = R < 2048 ? static_cast<int>(R) : 2048;  // 8 blocks/CU (see LN note)
   int ecpt = (C + LN_BLOCK - 1) / LN_BLOCK;
@@ -415,6 +440,7 @@ __global__ void k_colsum_bf16(const uint16_t* __restrict__ x,
 void hip_colsum_bf16(const void* x, float* out, int64_t R, int C,
                      hipStream_t s) {
   if (C > LN_MAXC) throw std::runtime_error("colsum: C too large");
+  if (R <= 0) return;  // out stays as the caller zeroed it
   int g = R < 2048 ? static_cast<int>(R) : 2048;
   int ecpt = (C + LN_BLOCK - 1) / LN_BLOCK;
   auto launch = [&](auto kern) {
@@ -434,6 +460,11 @@ void hip_ln_fwd(const void* x, const void* w, const void* b, void* y,
                 float* mean, float* rstd, int64_t R, int C, float eps,
                 hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("ln: bad C");
+  ln_check_align(x, "x");
+  ln_check_align(w, "weight");
+  ln_check_align(b, "bias");
+  ln_check_align(y, "y");
+  if (R <= 0) return;
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(R)), dim3(LN_BLOCK), 0,
@@ -446,8 +477,7 @@ void hip_ln_fwd(const void* x, const void* w, const void* b, void* y,
   else if (cpt <= 2) launch(k_ln_fwd<2>);
   else if (cpt <= 3) launch(k_ln_fwd<3>);
   else if (cpt <= 4) launch(k_ln_fwd<4>);
-  else if (cpt <= 8) launch(k_ln_fwd<8>);
-  else launch(k_ln_fwd<16>);
+  else launch(k_ln_fwd<8>);  // C <= LN_MAXC: cpt <= 8
   HIP_CHECK_LN(hipGetLastError());
 }
 
@@ -455,6 +485,11 @@ void hip_ln_bwd(const void* dy, const void* x, const void* w,
                 const float* mean, const float* rstd, void* dx, float* dgamma,
                 float* dbeta, int64_t R, int C, hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("ln: bad C");
+  ln_check_align(dy, "dy");
+  ln_check_align(x, "x");
+  ln_check_align(w, "weight");
+  ln_check_align(dx, "dx");
+  if (R <= 0) return;  // dgamma/dbeta stay as the caller zeroed them
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch_dx = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(R)), dim3(LN_BLOCK), 0,
@@ -467,8 +502,7 @@ void hip_ln_bwd(const void* dy, const void* x, const void* w,
   else if (cpt <= 2) launch_dx(k_ln_bwd_dx<2>);
   else if (cpt <= 3) launch_dx(k_ln_bwd_dx<3>);
   else if (cpt <= 4) launch_dx(k_ln_bwd_dx<4>);
-  else if (cpt <= 8) launch_dx(k_ln_bwd_dx<8>);
-  else launch_dx(k_ln_bwd_dx<16>);
+  else launch_dx(k_ln_bwd_dx<8>);  // C <= LN_MAXC: cpt <= 8
   HIP_CHECK_LN(hipGetLastError());
   // 2048 blocks = 8 per CU: enough waves to hide the strided bf16 loads
   // (256 blocks measured 0.67 TB/s — latency-bound at 1 block/CU); the

@@ -91,13 +91,25 @@ __global__ void k_swiglu_bwd(const uint4* __restrict__ dy,
       float a0 = sw_lo(ap[k]), a1 = sw_hi(ap[k]);
       float b0 = sw_lo(bp[k]), b1 = sw_hi(bp[k]);
       float sg0 = sw_sigmoid(a0), sg1 = sw_sigmoid(a1);
-      o1p[k] = sw_pack(g0 * b0 * sg0 * (1.f + a0 * (1.f - sg0)),
-                       g1 * b1 * sg1 * (1.f + a1 * (1.f - sg1)));
-      o3p[k] = sw_pack(g0 * a0 * sg0, g1 * a1 * sg1);
+      // the bounded factors silu'(a) and silu(a) first: dy * x3 or dy * x1
+      // alone can overflow to inf where they have underflowed to 0, and
+      // inf * 0 is NaN where the gradient is 0
+      float d0 = sg0 * (1.f + a0 * (1.f - sg0));
+      float d1 = sg1 * (1.f + a1 * (1.f - sg1));
+      o1p[k] = sw_pack(g0 * (b0 * d0), g1 * (b1 * d1));
+      o3p[k] = sw_pack(g0 * (a0 * sg0), g1 * (a1 * sg1));
     }
     dx1[i] = o1;
     dx3[i] = o3;
   }
+}
+
+// uint4 loads and stores: every pointer must be 16-byte aligned (the Python
+// wrapper clones an offset view that is not).
+static void sw_check_align(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) & 15u)
+    throw std::runtime_error(std::string("swiglu: ") + what +
+                             " is not 16-byte aligned");
 }
 
 static inline int sw_grid(int64_t n8) {
@@ -108,6 +120,10 @@ static inline int sw_grid(int64_t n8) {
 void hip_swiglu_fwd(const void* x1, const void* x3, void* y, int64_t n,
                     hipStream_t s) {
   if (n % 8) throw std::runtime_error("swiglu: n must be a multiple of 8");
+  sw_check_align(x1, "x1");
+  sw_check_align(x3, "x3");
+  sw_check_align(y, "y");
+  if (n <= 0) return;
   int64_t n8 = n / 8;
   hipLaunchKernelGGL(k_swiglu_fwd, dim3(sw_grid(n8)), dim3(SW_BLOCK), 0, s,
                      static_cast<const uint4*>(x1),
@@ -119,6 +135,12 @@ void hip_swiglu_fwd(const void* x1, const void* x3, void* y, int64_t n,
 void hip_swiglu_bwd(const void* dy, const void* x1, const void* x3, void* dx1,
                     void* dx3, int64_t n, hipStream_t s) {
   if (n % 8) throw std::runtime_error("swiglu: n must be a multiple of 8");
+  sw_check_align(dy, "dy");
+  sw_check_align(x1, "x1");
+  sw_check_align(x3, "x3");
+  sw_check_align(dx1, "dx1");
+  sw_check_align(dx3, "dx3");
+  if (n <= 0) return;
   int64_t n8 = n / 8;
   hipLaunchKernelGGL(k_swiglu_bwd, dim3(sw_grid(n8)), dim3(SW_BLOCK), 0, s,
                      static_cast<const uint4*>(dy),

@@ -25,10 +25,17 @@ from .. import _core
 MAX_C = 4096  # per-thread register accumulators in the dgamma kernel
 
 
+def _pair_aligned(t):
+    """The block-per-row kernels load bf16 pairs as uint32.  contiguous()
+    keeps an offset view of a larger buffer as it is; a copy aligns it."""
+    return t.clone() if t.data_ptr() % 4 else t
+
+
 class _FusedRMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
-        x = x.contiguous()
+        x = _pair_aligned(x.contiguous())
+        weight = _pair_aligned(weight)
         C = x.shape[-1]
         R = x.numel() // C
         y = torch.empty_like(x)
@@ -42,7 +49,7 @@ class _FusedRMSNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _pair_aligned(dy.contiguous())
         C = x.shape[-1]
         R = x.numel() // C
         dx = torch.empty_like(x)

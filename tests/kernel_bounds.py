@@ -1,0 +1,435 @@
+"""fp64 references and derived error bounds for the bf16 model kernels
+(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU).
+
+Reference: the same formula evaluated in fp64 on the bf16 inputs; backward
+references use fp64 statistics, never the kernel's saved mean / rstd.
+
+Bound for a bf16 output element:
+
+    |got - ref| <= 1 bf16 ulp at |ref| + slack
+
+One ulp = half an ulp for the final round-to-nearest-even + half an ulp for
+a rounding that fp32 error flipped.  Below the smallest normal bf16 (2^-126)
+the allowance is 2^-126 itself, so a flushed subnormal is accepted.  `slack`
+is the running-error bound of an fp32 evaluation, n * 2^-24 * sum|terms|,
+computed here in fp64 next to the reference: it is derived from the formula
+and the reduction depth, not measured.  fp32 outputs (mean, rstd, dgamma,
+dbeta, colsum) are held to the slack alone.
+
+Reduction depth.  A row statistic is summed by 256 threads: each adds its
+ceil(C/512) bf16 pairs serially (2 adds per pair), then 6 shuffle levels and
+3 LDS adds, then one divide: n_red(C) = 2*ceil(C/512) + 10.  Column sums
+over R rows are bounded for any order (serial, atomics): n = R + 3.
+
+Transcendentals.  tanhf is given 4 fp32 ulps of its value.  The fast exp is
+exp2(x * log2(e)) with the product rounded to fp32, a relative error of
+|x| * 2^-24 in the result, plus 3 ulps for the exp2 and the constant.  A
+sigmoid below the smallest normal fp32 may flush or saturate to 0 (exp
+overflows to inf at x < -88.7), an absolute error of 2^-126 that the
+multiplications by x1, x3 and dy then scale.
+
+Every formula below takes a dtype, so the CPU self-test can run the very
+same code in fp32, round to bf16 and push it through the bound: a bound the
+fp32 evaluation of the reference cannot meet would be one no kernel can.
+"""
+import math
+
+import numpy as np
+import torch
+
+U = 2.0 ** -24            # fp32 unit roundoff
+ETA = 2.0 ** -126         # smallest normal fp32 (and bf16)
+BF16_MIN_NORMAL = 2.0 ** -126
+BF16_MAX = float(torch.finfo(torch.bfloat16).max)
+TANH_ULPS = 4.0
+GK = math.sqrt(2.0 / math.pi)
+GC = 0.044715
+EPS = 1e-5
+EPS32 = float(np.float32(EPS))  # what the kernel receives
+
+
+def n_red(C: int) -> int:
+    return 2 * math.ceil(C / 512) + 10
+
+
+# ------------------------------------------------------------------ bound
+
+def bf16_ulp(ref: torch.Tensor) -> torch.Tensor:
+    """Spacing of bf16 (8 significant bits) at |ref|; 2^-126 below the
+    smallest normal."""
+    a = ref.double().abs()
+    _, e = torch.frexp(a.clamp_min(BF16_MIN_NORMAL))  # a = m * 2^e, m in [.5, 1)
+    ulp = torch.ldexp(torch.ones_like(a), e - 8)
+    return torch.where(a < BF16_MIN_NORMAL,
+                       torch.full_like(a, BF16_MIN_NORMAL), ulp)
+
+
+def violations(got, ref, slack, ulps=1.0):
+    """Boolean mask of elements outside the bound, and the largest error in
+    bf16 ulps over the finite elements.  A NaN reference is not judged, an
+    infinite one must be met exactly, and a finite one within reach of the
+    bf16 maximum may come out as the infinity of its sign."""
+    got = got.double()
+    ref = ref.double()
+    ulp = bf16_ulp(ref)
+    tol = ulps * ulp + slack
+    err = (got - ref).abs()
+    ok = err <= tol
+    inf = torch.full_like(ref, float("inf")).copysign(ref)
+    ok |= (ref.abs() + tol >= BF16_MAX) & (got == inf)
+    ok = torch.where(torch.isinf(ref), got == ref, ok)
+    ok |= torch.isnan(ref)
+    # reported figure: elements whose slack is below one ulp, where the
+    # bf16 ulp is the meaningful unit (an ill-conditioned element, such as
+    # silu(-90) * 3e38, is judged by its slack and says nothing in ulps)
+    judged = torch.isfinite(ref) & torch.isfinite(got) & (slack <= ulp)
+    worst = float((err / ulp)[judged].max()) if judged.any() else 0.0
+    return ~ok, worst
+
+
+def report(op, out, family, worst, unit="bf16ulp"):
+    print(f"MAXERR op={op} out={out} family={family} {worst:.4g} {unit}")
+
+
+def assert_bf16(got, ref, slack, op, out, family, ulps=1.0):
+    bad, worst = violations(got, ref, slack, ulps)
+    report(op, out, family, worst)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        g, r = float(got[i]), float(ref[i])
+        s = float(slack[i]) if slack.dim() else float(slack)
+        raise AssertionError(
+            f"{op} {out} [{family}]: {int(bad.sum())} of {bad.numel()} "
+            f"elements outside 1 ulp + slack; first at {i}: got {g!r}, "
+            f"ref {r!r}, ulp {float(bf16_ulp(ref[i])):.3g}, slack {s:.3g}")
+    return worst
+
+
+def assert_f32(got, ref, slack, op, out, family):
+    """fp32 output: slack plus the one fp32 rounding of the stored value."""
+    got = got.double()
+    ref = ref.double()
+    tol = slack + U * ref.abs() + 2.0 ** -149
+    err = (got - ref).abs()
+    worst = float((err / tol).max()) if err.numel() else 0.0
+    report(op, out, family, worst, unit="of-slack")
+    bad = ~(err <= tol)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(
+            f"{op} {out} [{family}]: {int(bad.sum())} of {bad.numel()} "
+            f"outside the fp32 bound; first at {i}: got {float(got[i])!r}, "
+            f"ref {float(ref[i])!r}, tol {float(tol[i]):.3g}")
+    return worst
+
+
+# ------------------------------------------------------------ norm formulas
+
+def rms_formula(x, w, dy=None, dtype=torch.float64, eps=EPS32):
+    x, w = x.to(dtype), w.to(dtype)
+    rs = torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
+    out = {"y": x * rs * w, "rstd": rs.squeeze(-1)}
+    if dy is not None:
+        g = dy.to(dtype) * w
+        t = rs * rs * (g * x).mean(-1, keepdim=True)
+        out["dx"] = rs * (g - x * t)
+        out["dgamma"] = (dy.to(dtype) * x * rs).sum(0)
+    return out
+
+
+def rms_slack(x, w, dy=None, eps=EPS32):
+    """Running-error bounds for rms_formula evaluated in fp32."""
+    x, w = x.double(), w.double()
+    R, C = x.shape
+    n = n_red(C)
+    rs = torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
+    # sum of squares: all terms positive, relative error (n + 2)u; the
+    # inverse square root halves it; 4u for add, divide and rsqrt
+    d_rs = (0.5 * (n + 2) + 4) * U
+    y = x * rs * w
+    out = {"y": y.abs() * (d_rs + 3 * U), "rstd": (rs * d_rs).squeeze(-1)}
+    if dy is not None:
+        dy = dy.double()
+        g = dy * w
+        gx = g * x
+        t = rs * rs * gx.mean(-1, keepdim=True)
+        t_err = (rs * rs * (n + 3) * U * gx.abs().mean(-1, keepdim=True)
+                 + t.abs() * (2 * d_rs + 3 * U))
+        mag = g.abs() + (x * t).abs()
+        dx = rs * (g - x * t)
+        out["dx"] = (rs * (3 * U * mag + x.abs() * t_err) + d_rs * rs * mag
+                     + U * dx.abs())
+        out["dgamma"] = ((R + 3) * U + d_rs) * (dy * x * rs).abs().sum(0)
+    return out
+
+
+def ln_formula(x, w, b=None, dy=None, dtype=torch.float64, eps=EPS32):
+    x, w = x.to(dtype), w.to(dtype)
+    m = x.mean(-1, keepdim=True)
+    d = x - m
+    rs = torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    h = d * rs
+    y = h * w
+    if b is not None:
+        y = y + b.to(dtype)
+    out = {"y": y, "mean": m.squeeze(-1), "rstd": rs.squeeze(-1)}
+    if dy is not None:
+        dy = dy.to(dtype)
+        g = dy * w
+        t1 = g.mean(-1, keepdim=True)
+        t2 = (g * h).mean(-1, keepdim=True)
+        out["dx"] = rs * (g - t1 - h * t2)
+        out["dgamma"] = (dy * h).sum(0)
+        out["dbeta"] = dy.sum(0)
+    return out
+
+
+def ln_slack(x, w, b=None, dy=None, eps=EPS32):
+    """Running-error bounds for ln_formula evaluated in fp32 (two-pass
+    variance)."""
+    x, w = x.double(), w.double()
+    R, C = x.shape
+    n = n_red(C)
+    m = x.mean(-1, keepdim=True)
+    d = x - m
+    var = (d * d).mean(-1, keepdim=True)
+    rs = torch.rsqrt(var + eps)
+    h = d * rs
+    m_err = n * U * x.abs().mean(-1, keepdim=True)
+    # (x - m)^2 with m off by m_err, then a sum of positive terms
+    var_err = (2 * m_err * d.abs().mean(-1, keepdim=True) + m_err * m_err
+               + (n + 3) * U * var)
+    rs_err = 0.5 * rs ** 3 * var_err + 3 * U * rs
+    h_err = rs * (m_err + U * d.abs()) + d.abs() * rs_err + U * h.abs()
+    babs = b.double().abs() if b is not None else 0.0
+    out = {"y": w.abs() * h_err + 3 * U * ((h * w).abs() + babs),
+           "mean": m_err.squeeze(-1), "rstd": rs_err.squeeze(-1)}
+    if dy is not None:
+        dy = dy.double()
+        g = dy * w
+        t1 = g.mean(-1, keepdim=True)
+        t2 = (g * h).mean(-1, keepdim=True)
+        t1_err = (n + 1) * U * g.abs().mean(-1, keepdim=True)
+        t2_err = ((n + 3) * U * (g * h).abs().mean(-1, keepdim=True)
+                  + (g.abs() * h_err).mean(-1, keepdim=True))
+        inner = g - t1 - h * t2
+        inner_err = (t1_err + h.abs() * t2_err + t2.abs() * h_err
+                     + 4 * U * (g.abs() + t1.abs() + (h * t2).abs()))
+        out["dx"] = (rs * inner_err + rs_err * inner.abs()
+                     + U * (rs * inner).abs())
+        out["dgamma"] = ((dy.abs() * h_err).sum(0)
+                         + (R + 3) * U * (dy * h).abs().sum(0))
+        out["dbeta"] = (R + 1) * U * dy.abs().sum(0)
+    return out
+
+
+# ------------------------------------------------- kernel-order emulation
+
+def emu_block_sum(v: np.ndarray) -> np.ndarray:
+    """The kernels' block_sum in fp32: v is (..., 256) per-thread partials;
+    a shuffle-down tree inside each 64-lane wave, then ((w0+w1)+w2)+w3."""
+    a = v.astype(np.float32).reshape(v.shape[:-1] + (4, 64)).copy()
+    w = 32
+    while w:
+        a[..., :w] = a[..., :w] + a[..., w:2 * w]
+        w >>= 1
+    l = a[..., 0]
+    return ((l[..., 0] + l[..., 1]) + l[..., 2]) + l[..., 3]
+
+
+def emu_ln_stats(x: torch.Tensor, one_pass: bool, eps=EPS32):
+    """mean and rstd of each row of bf16 x as k_ln_fwd's thread layout and
+    fp32 summation order give them: thread t owns the bf16 pairs t, t+256,
+    ...; `one_pass` is the E[x^2] - m^2 form the kernel used to have."""
+    f = np.float32
+    xs = x.float().numpy().astype(f)
+    R, C = xs.shape
+    C2 = C // 2
+    cpt = (C2 + 255) // 256
+    pad = np.zeros((R, cpt * 256, 2), f)
+    pad[:, :C2] = xs.reshape(R, C2, 2)
+    valid = (np.arange(cpt * 256) < C2).reshape(cpt, 256)
+    lo = pad[..., 0].reshape(R, cpt, 256)
+    hi = pad[..., 1].reshape(R, cpt, 256)
+    s = np.zeros((R, 256), f)
+    ss = np.zeros((R, 256), f)
+    for k in range(cpt):
+        s = s + (lo[:, k] + hi[:, k])
+        ss = ss + (lo[:, k] * lo[:, k] + hi[:, k] * hi[:, k])
+    m = emu_block_sum(s) / f(C)
+    if one_pass:
+        var = emu_block_sum(ss) / f(C) - m * m
+        arg = np.where(var > 0, var + f(eps), f(eps)).astype(f)
+    else:
+        ss = np.zeros((R, 256), f)
+        for k in range(cpt):
+            d0 = lo[:, k] - m[:, None]
+            d1 = hi[:, k] - m[:, None]
+            ss = ss + np.where(valid[k], d0 * d0 + d1 * d1, f(0)).astype(f)
+        arg = (emu_block_sum(ss) / f(C) + f(eps)).astype(f)
+    rs = (f(1) / np.sqrt(arg)).astype(f)
+    return torch.from_numpy(m), torch.from_numpy(rs)
+
+
+# --------------------------------------------------------- norm input sets
+
+NORM_FAMILIES = ["randn2", "shifted", "constant", "outlier", "zero_dy",
+                 "w_zeros"]
+
+
+def norm_inputs(family, R, C, seed=0, device="cpu"):
+    """bf16 x (R, C), w, b (C), dy (R, C).  Generated on the CPU so the CPU
+    self-test and the GPU tests see the same numbers."""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * R + C)
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+    x = rn(R, C, scale=2.0)
+    w, b, dy = rn(C), rn(C), rn(R, C)
+    if family == "shifted":      # |mean| >> std: E[x^2] - m^2 cancels
+        x = torch.full((R, C), 100.0)
+        x[:, ::317] = 100.5
+    elif family == "constant":   # variance exactly 0
+        x = (1.5 * torch.arange(1, R + 1.0))[:, None].expand(R, C).clone()
+    elif family == "outlier":
+        x = rn(R, C)
+        x[:, C // 3] = 1e4
+    elif family == "zero_dy":
+        dy = torch.zeros(R, C)
+    elif family == "w_zeros":
+        w[::3] = 0.0
+    elif family != "randn2":
+        raise ValueError(family)
+    return tuple(t.to(torch.bfloat16).to(device) for t in (x, w, b, dy))
+
+
+# -------------------------------------------------------------- elementwise
+
+def all_bf16(device="cpu"):
+    """Every bf16 bit pattern, in bit order (65536 values)."""
+    bits = torch.arange(65536, dtype=torch.int32).to(torch.int16)
+    return bits.view(torch.bfloat16).to(device)
+
+
+def dy_pattern(n, device="cpu"):
+    """A fixed second dy: finite, both signs, zeros, 2^-20 .. 2^20."""
+    i = torch.arange(n, dtype=torch.float64)
+    mant = ((i * 37) % 17 - 8) / 8.0            # -1 .. 1, 0 included
+    expo = torch.exp2(((i * 11) % 41) - 20)
+    return (mant * expo).to(torch.bfloat16).to(device)
+
+
+def gelu_formula(x, dy=None, dtype=torch.float64, clamp=False):
+    """tanh-approximate GELU.  `clamp` evaluates the derivative at x clamped
+    to [-10, 10], where it has long reached 1 or 0: what an fp32 evaluation
+    has to do, since x*x overflows for |x| > 1.8e19."""
+    x = x.to(dtype)
+    t = torch.tanh(GK * (x + GC * x * x * x))
+    out = {"y": 0.5 * x * (1 + t)}
+    if dy is not None:
+        xc = torch.where(x.isnan(), x, x.clamp(-10, 10)) if clamp else x
+        x2 = xc * xc
+        inner = GK * xc * (1 + GC * x2)
+        tc = torch.tanh(inner)
+        # fp64 reference: 1/cosh^2 has no cancellation; fp32: as the kernel
+        sech2 = (1 - tc * tc) if clamp else 1 / torch.cosh(inner) ** 2
+        grad = 0.5 * (1 + tc) + 0.5 * xc * sech2 * GK * (1 + 3 * GC * x2)
+        out["dx"] = dy.to(dtype) * grad
+    return out
+
+
+def gelu_slack(x, dy=None):
+    x = x.double()
+    inner = GK * (x + GC * x * x * x)
+    t = torch.tanh(inner)
+    sech2 = 1 / torch.cosh(inner) ** 2
+    t_err = sech2 * 7 * U * inner.abs() + TANH_ULPS * U * t.abs()
+    t_err = torch.where(torch.isfinite(t_err), t_err, TANH_ULPS * U)
+    y = 0.5 * x * (1 + t)
+    out = {"y": 0.5 * x.abs() * (t_err + U * (1 + t.abs())) + 2 * U * y.abs()}
+    if dy is not None:
+        # the bound is the one at min(|x|, 10): beyond that the derivative
+        # is constant to 1e-36 and no evaluation has to be less accurate
+        xc = x.clamp(-10, 10)
+        ic = GK * xc * (1 + GC * xc * xc)
+        tc = torch.tanh(ic)
+        s2 = 1 / torch.cosh(ic) ** 2
+        tc_err = s2 * 7 * U * ic.abs() + TANH_ULPS * U * tc.abs()
+        a_err = 0.5 * (tc_err + U * (1 + tc.abs()))
+        s2_err = 2 * tc.abs() * tc_err + 2 * U       # 1 - t*t, absolute
+        p = 0.5 * xc * GK * (1 + 3 * GC * xc * xc)
+        b_err = p.abs() * s2_err + 7 * U * (p * s2).abs()
+        grad = 0.5 * (1 + tc) + p * s2
+        out["dx"] = dy.double().abs() * (a_err + b_err + 2 * U * grad.abs())
+    return out
+
+
+def swiglu_formula(x1, x3, dy=None, dtype=torch.float64):
+    a, b = x1.to(dtype), x3.to(dtype)
+    sg = 1 / (1 + torch.exp(-a))
+    out = {"y": a * sg * b}
+    if dy is not None:
+        g = dy.to(dtype)
+        # bounded factors first: silu'(a) and silu(a) underflow to 0 where
+        # dy * x3 or dy * x1 alone would overflow to inf, and inf * 0 = NaN
+        out["dx1"] = g * (b * (sg * (1 + a * (1 - sg))))
+        out["dx3"] = g * (a * sg)
+    return out
+
+
+def swiglu_slack(x1, x3, dy=None):
+    a, b = x1.double(), x3.double()
+    sg = 1 / (1 + torch.exp(-a))
+    nsg = 1 / (1 + torch.exp(a))                 # 1 - sg without cancellation
+    sg_err = sg * nsg * (a.abs() + 3) * U + 2 * U * sg + ETA
+    ab = (a * b).abs()
+    y = a * sg * b
+    out = {"y": ab * sg_err + 2 * U * y.abs()}
+    if dy is not None:
+        g = dy.double()
+        q = 1 + a * nsg
+        q_err = a.abs() * (sg_err + U * nsg) + 2 * U * (1 + (a * nsg).abs())
+        gb = (g * b).abs()
+        out["dx1"] = (gb * (sg_err * q.abs() + sg * q_err)
+                      + 3 * U * (g * b * sg * q).abs())
+        out["dx3"] = (g * a).abs() * sg_err + 2 * U * (g * a * sg).abs()
+    for k, v in out.items():                      # inf * 0 in the bound itself
+        out[k] = torch.where(torch.isnan(v), torch.full_like(v, float("inf")),
+                             v)
+    return out
+
+
+# ----------------------------------------------- wrapper-level norm checks
+
+def check_ln_wrapper(fused_layer_norm, x, w, b, dy, family, eps=EPS):
+    """fused_layer_norm forward + backward on 2-D bf16 inputs against the
+    fp64 reference: y, dx, and the bf16 weight gradients, each 1 ulp +
+    slack.  Returns the kernel's outputs."""
+    xf = x.clone().requires_grad_(True)
+    wf = w.clone().requires_grad_(True)
+    bf = b.clone().requires_grad_(True) if b is not None else None
+    y = fused_layer_norm(xf, wf, bf, eps)
+    y.backward(dy)
+    ref = ln_formula(x, w, b, dy)
+    slack = ln_slack(x, w, b, dy)
+    got = {"y": y.detach(), "dx": xf.grad, "dgamma": wf.grad}
+    if b is not None:
+        got["dbeta"] = bf.grad
+    for k, v in got.items():
+        assert v.dtype == torch.bfloat16 and v.shape == ref[k].shape, k
+        assert_bf16(v, ref[k], slack[k], "ln", k, family)
+    return got
+
+
+def check_rms_wrapper(fused_rms_norm, x, w, dy, family, eps=EPS):
+    xf = x.clone().requires_grad_(True)
+    wf = w.clone().requires_grad_(True)
+    y = fused_rms_norm(xf, wf, eps)
+    y.backward(dy)
+    ref = rms_formula(x, w, dy)
+    slack = rms_slack(x, w, dy)
+    got = {"y": y.detach(), "dx": xf.grad, "dgamma": wf.grad}
+    for k, v in got.items():
+        assert v.dtype == torch.bfloat16 and v.shape == ref[k].shape, k
+        assert_bf16(v, ref[k], slack[k], "rms", k, family)
+    return got

@@ -2,6 +2,7 @@
 import pytest
 import torch
 
+import kernel_bounds as kb
 from sharedtensor_amd.ops import fused_ln
 
 pytestmark = pytest.mark.gpu
@@ -10,11 +11,19 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("R,C", [(128, 768), (1000, 768), (64, 1536),
                                  (32, 64), (7, 4096)])
 def test_fwd_bwd_matches_torch(R, C):
+    """y, dx, dgamma and dbeta within 1 bf16 ulp + the derived fp32 slack of
+    the fp64 reference (tests/kernel_bounds.py), which is inside the fixed
+    tolerances this test used to have (2e-2 on y, 5e-2 on dx, atol 3e-1 on
+    the weight gradients), kept below against torch's own layer_norm."""
     torch.manual_seed(R + C)
     x = (torch.randn(R, C, device="cuda") * 2).to(torch.bfloat16)
     w = torch.randn(C, device="cuda").to(torch.bfloat16)
     b = torch.randn(C, device="cuda").to(torch.bfloat16)
     dy = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+
+    got = kb.check_ln_wrapper(fused_ln.fused_layer_norm, x, w, b, dy,
+                              f"randn2/R={R}/C={C}")
+    torch.cuda.synchronize()
 
     # torch reference (bf16 in/out, fp32 internals — same contract)
     xt = x.clone().requires_grad_(True)
@@ -22,21 +31,14 @@ def test_fwd_bwd_matches_torch(R, C):
     bt = b.clone().requires_grad_(True)
     yt = torch.nn.functional.layer_norm(xt, (C,), wt, bt, 1e-5)
     yt.backward(dy)
-
-    xf = x.clone().requires_grad_(True)
-    wf = w.clone().requires_grad_(True)
-    bf = b.clone().requires_grad_(True)
-    yf = fused_ln.fused_layer_norm(xf, wf, bf, 1e-5)
-    yf.backward(dy)
-    torch.cuda.synchronize()
-
-    torch.testing.assert_close(yf.float(), yt.float(), rtol=2e-2, atol=2e-2)
-    torch.testing.assert_close(xf.grad.float(), xt.grad.float(), rtol=5e-2,
+    torch.testing.assert_close(got["y"].float(), yt.float(), rtol=2e-2,
+                               atol=2e-2)
+    torch.testing.assert_close(got["dx"].float(), xt.grad.float(), rtol=5e-2,
                                atol=5e-2)
-    torch.testing.assert_close(wf.grad.float(), wt.grad.float(), rtol=3e-2,
-                               atol=3e-1)
-    torch.testing.assert_close(bf.grad.float(), bt.grad.float(), rtol=3e-2,
-                               atol=3e-1)
+    torch.testing.assert_close(got["dgamma"].float(), wt.grad.float(),
+                               rtol=3e-2, atol=3e-1)
+    torch.testing.assert_close(got["dbeta"].float(), bt.grad.float(),
+                               rtol=3e-2, atol=3e-1)
 
 
 def test_3d_input_and_model_path():

@@ -3,6 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_bounds as kb
 from sharedtensor_amd.ops import fused_swiglu
 
 pytestmark = pytest.mark.gpu
@@ -27,6 +28,14 @@ def test_fwd_bwd_matches_fp32_torch(shape):
     yf.backward(dy)
     torch.cuda.synchronize()
 
+    # 1 bf16 ulp + derived fp32 slack of the fp64 reference
+    ref = kb.swiglu_formula(x1, x3, dy)
+    slack = kb.swiglu_slack(x1, x3, dy)
+    fam = "randn*2/" + "x".join(map(str, shape))
+    kb.assert_bf16(yf.detach(), ref["y"], slack["y"], "swiglu", "y", fam)
+    kb.assert_bf16(af.grad, ref["dx1"], slack["dx1"], "swiglu", "dx1", fam)
+    kb.assert_bf16(bf.grad, ref["dx3"], slack["dx3"], "swiglu", "dx3", fam)
+    # and the fixed tolerances against the fp32 torch reference, as before
     torch.testing.assert_close(yf.float(), yt.float(), rtol=3e-2, atol=3e-2)
     torch.testing.assert_close(af.grad.float(), a.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(bf.grad.float(), b.grad, rtol=5e-2, atol=5e-2)
