@@ -138,6 +138,74 @@ void py_gpu_fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double mu,
                 reinterpret_cast<hipStream_t>(stream));
 }
 
+// dsts[0] = fp32 values (required: the kernel reads the pre-update weight);
+// dsts[1..3] = delta-typed
+void py_gpu_fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
+                           uintptr_t shadow_bf16, double lr, double mu,
+                           int64_t n, std::vector<uintptr_t> dsts,
+                           uintptr_t stream, bool delta_bf16) {
+  uintptr_t d[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
+  if (!d[0] || !shadow_bf16)
+    throw std::runtime_error("gpu_fused_sgd_bf16: values and shadow required");
+  hip_fused_sgd_bf16(reinterpret_cast<float*>(mom),
+                     reinterpret_cast<const uint16_t*>(grad_bf16),
+                     reinterpret_cast<uint16_t*>(shadow_bf16),
+                     static_cast<float>(lr), static_cast<float>(mu), n,
+                     reinterpret_cast<float*>(d[0]),
+                     reinterpret_cast<void*>(d[1]),
+                     reinterpret_cast<void*>(d[2]),
+                     reinterpret_cast<void*>(d[3]), delta_bf16,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
+// dsts[0] = fp32 values (required); dsts[1..3] = delta-typed.  shadow may be
+// 0.  inv_bc1/2 = 1/(1-beta^t), rounded to fp32 here as Engine::fused_adamw
+// hands them to the kernel.
+void py_gpu_fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
+                        bool grad_bf16, uintptr_t shadow_bf16, double lr,
+                        double beta1, double beta2, double eps, double wd,
+                        double inv_bc1, double inv_bc2, int64_t n,
+                        std::vector<uintptr_t> dsts, uintptr_t stream,
+                        bool delta_bf16) {
+  uintptr_t d[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
+  if (!d[0]) throw std::runtime_error("gpu_fused_adamw: values required");
+  hip_fused_adamw(reinterpret_cast<float*>(mom), reinterpret_cast<float*>(vel),
+                  reinterpret_cast<const void*>(grad), grad_bf16,
+                  reinterpret_cast<uint16_t*>(shadow_bf16),
+                  static_cast<float>(lr), static_cast<float>(beta1),
+                  static_cast<float>(beta2), static_cast<float>(eps),
+                  static_cast<float>(wd), static_cast<float>(inv_bc1),
+                  static_cast<float>(inv_bc2), n,
+                  reinterpret_cast<float*>(d[0]),
+                  reinterpret_cast<void*>(d[1]), reinterpret_cast<void*>(d[2]),
+                  reinterpret_cast<void*>(d[3]), delta_bf16,
+                  reinterpret_cast<hipStream_t>(stream));
+}
+
+// out := values (fp32), delta -= values (delta-typed)
+void py_gpu_snapshot_capture(uintptr_t values, uintptr_t delta, uintptr_t out,
+                             int64_t n, uintptr_t stream, bool delta_bf16) {
+  hip_snapshot_capture(reinterpret_cast<const float*>(values),
+                       reinterpret_cast<void*>(delta), delta_bf16,
+                       reinterpret_cast<float*>(out), n,
+                       reinterpret_cast<hipStream_t>(stream));
+}
+
+// src is delta-typed; dsts[0] = fp32 values (or 0); dsts[1..2] = delta-typed
+void py_gpu_add_delta_scatter(uintptr_t src, int64_t n,
+                              std::vector<uintptr_t> dsts, uintptr_t stream,
+                              bool delta_bf16) {
+  uintptr_t d[3] = {0, 0, 0};
+  for (size_t i = 0; i < dsts.size() && i < 3; ++i) d[i] = dsts[i];
+  hip_add_delta_scatter(reinterpret_cast<const void*>(src), delta_bf16, n,
+                        reinterpret_cast<float*>(d[0]),
+                        reinterpret_cast<void*>(d[1]),
+                        reinterpret_cast<void*>(d[2]),
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_core, m) {
@@ -225,6 +293,22 @@ PYBIND11_MODULE(_core, m) {
   m.def("gpu_fused_sgd", &py_gpu_fused_sgd, py::arg("mom"), py::arg("grad"),
         py::arg("lr"), py::arg("mu"), py::arg("n"), py::arg("dsts"),
         py::arg("stream"), py::arg("delta_bf16") = false);
+  m.def("gpu_fused_sgd_bf16", &py_gpu_fused_sgd_bf16, py::arg("mom"),
+        py::arg("grad"), py::arg("shadow"), py::arg("lr"), py::arg("mu"),
+        py::arg("n"), py::arg("dsts"), py::arg("stream"),
+        py::arg("delta_bf16") = false);
+  m.def("gpu_fused_adamw", &py_gpu_fused_adamw, py::arg("mom"),
+        py::arg("vel"), py::arg("grad"), py::arg("grad_bf16"),
+        py::arg("shadow"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("wd"), py::arg("inv_bc1"), py::arg("inv_bc2"),
+        py::arg("n"), py::arg("dsts"), py::arg("stream"),
+        py::arg("delta_bf16") = false);
+  m.def("gpu_snapshot_capture", &py_gpu_snapshot_capture, py::arg("values"),
+        py::arg("delta"), py::arg("out"), py::arg("n"), py::arg("stream"),
+        py::arg("delta_bf16") = false);
+  m.def("gpu_add_delta_scatter", &py_gpu_add_delta_scatter, py::arg("src"),
+        py::arg("n"), py::arg("dsts"), py::arg("stream"),
+        py::arg("delta_bf16") = false);
   m.def("rccl_loopback_payload", &rccl_loopback_payload,
         "Self ncclSend/ncclRecv of a real payload on one device (1-rank "
         "comm): executes the non-blocking enqueue ordering + stream polling "

@@ -66,6 +66,14 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
   return static_cast<uint16_t>(u >> 16);
 }
 
+// a + b rounded on its own.  The optimizers' u = -lr * (...) would otherwise
+// be contracted into the shadow's old + u, which then is no longer the
+// rounding of what atomicAdd(values, u) stored (visible where old ~ -u).
+__device__ __forceinline__ float add_uncontracted(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 // Residual-delta storage policies --------------------------------------
 
 struct DeltaF32 {
@@ -85,10 +93,11 @@ struct DeltaBF16 {
   }
   static __device__ __forceinline__ void atomic_add(T* p, int64_t i, float v) {
     // hardware packed bf16 atomic on the containing (even, odd) pair; the
-    // neighbour lane receives +0.0 (identity)
+    // neighbour lane receives -0.0, the exact identity (x + -0.0 == x for
+    // every x; +0.0 would turn a -0.0 neighbour into +0.0)
     auto* base = reinterpret_cast<__hip_bfloat162*>(p + (i & ~int64_t(1)));
     __hip_bfloat16 bv = __float2bfloat16(v);
-    __hip_bfloat16 bz = __float2bfloat16(0.0f);
+    __hip_bfloat16 bz = __float2bfloat16(-0.0f);
     __hip_bfloat162 val = (i & 1) ? __hip_bfloat162(bz, bv)
                                   : __hip_bfloat162(bv, bz);
     unsafeAtomicAdd(base, val);
@@ -165,12 +174,28 @@ __device__ __forceinline__ void wave_flush_sumsq(double acc, int t, double* sums
   if ((threadIdx.x & 63) == 0 && acc != 0.0) atomicAdd(&sumsq[t], acc);
 }
 
+// Maximum of two magnitudes (sign bit clear) through their bit patterns:
+// the order of non-negative floats, with +inf above every finite value and
+// NaN above +inf.  A float compare would drop a NaN; this way a poisoned
+// residual reaches k_finalize_scales, which answers it with scale 0.
+__device__ __forceinline__ float mag_max(float a, float b) {
+  uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
+  return __uint_as_float(ua > ub ? ua : ub);
+}
+
 __device__ __forceinline__ void wave_flush_max(float acc, int t, uint32_t* amax) {
-  for (int w = 32; w > 0; w >>= 1) {
-    float o = __shfl_down(acc, w, 64);
-    acc = o > acc ? o : acc;
-  }
-  if ((threadIdx.x & 63) == 0 && acc > 0.0f)
+  for (int w = 32; w > 0; w >>= 1) acc = mag_max(acc, __shfl_down(acc, w, 64));
+  if ((threadIdx.x & 63) == 0 && __float_as_uint(acc) != 0)
+    atomicMax(&amax[t], __float_as_uint(acc));
+}
+
+// Per-half-wave maximum for k_quant_int4, whose threads hold two elements
+// each: a tensor boundary (64 elements) can fall on lane 32, so each 32-lane
+// half reduces on its own and flushes into its own tensor's slot.  Call it
+// from wave-uniform control flow only.
+__device__ __forceinline__ void halfwave_flush_max(float acc, int t, uint32_t* amax) {
+  for (int w = 16; w > 0; w >>= 1) acc = mag_max(acc, __shfl_down(acc, w, 32));
+  if ((threadIdx.x & 31) == 0 && __float_as_uint(acc) != 0)
     atomicMax(&amax[t], __float_as_uint(acc));
 }
 
@@ -218,8 +243,7 @@ __global__ void k_reduce_absmax(const typename DP::T* __restrict__ delta,
     int64_t L = j - poffs[t];
     int64_t sz = offs[t + 1] - offs[t];
     if (L < sz) {
-      float v = fabsf(DP::load(delta, offs[t] + L));
-      acc = v > acc ? v : acc;
+      acc = mag_max(acc, fabsf(DP::load(delta, offs[t] + L)));
     }
   }
   if (cur_t >= 0) wave_flush_max(acc, cur_t, amax);
@@ -317,8 +341,7 @@ __global__ void k_quant_fp8(typename DP::T* __restrict__ delta,
         DP::atomic_add(delta, g, -sent);
       }
       if (stats_out) {
-        float r = fabsf(v - sent);
-        amax = r > amax ? r : amax;
+        amax = mag_max(amax, fabsf(v - sent));
       }
     }
     payload[j] = q;
@@ -334,7 +357,8 @@ __global__ void k_quant_int4(typename DP::T* __restrict__ delta,
   // one thread per payload byte = 2 elements (both in the same tensor:
   // padded regions are 64-aligned, hence even).  nb is only a multiple of
   // 32, so the loop runs to a 64-multiple with clamped indices to keep the
-  // wave fully convergent for the stats __shfl flush.
+  // wave fully convergent for the stats __shfl flush (clamped lanes fill a
+  // whole 32-lane half and share the last tensor).
   int64_t nb = pe / 2;
   int64_t nbp = (nb + 63) & ~int64_t(63);
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
@@ -344,8 +368,11 @@ __global__ void k_quant_int4(typename DP::T* __restrict__ delta,
     bool act = b < nb;
     int64_t j0 = (act ? b : nb - 1) * 2;
     int t = (T == 1) ? 0 : find_tensor(poffs, T, j0);
-    if (stats_out && t != cur_t) {
-      if (cur_t >= 0) wave_flush_max(amax, cur_t, stats_out);
+    // a wave covers 128 elements, so t is uniform over each 32-lane half
+    // only; the vote keeps the shuffles in wave-uniform control flow (the
+    // loop bound and cur_t >= 0 are wave-uniform too)
+    if (stats_out && __any(t != cur_t)) {
+      if (cur_t >= 0) halfwave_flush_max(amax, cur_t, stats_out);
       amax = 0.0f;
       cur_t = t;
     }
@@ -368,14 +395,13 @@ __global__ void k_quant_int4(typename DP::T* __restrict__ delta,
           DP::atomic_add(delta, g, -sent);
         }
         if (stats_out) {
-          float r2 = fabsf(v - sent);
-          amax = r2 > amax ? r2 : amax;
+          amax = mag_max(amax, fabsf(v - sent));
         }
       }
     }
     if (act) payload[b] = byte;
   }
-  if (stats_out && cur_t >= 0) wave_flush_max(amax, cur_t, stats_out);
+  if (stats_out && cur_t >= 0) halfwave_flush_max(amax, cur_t, stats_out);
 }
 
 // ------------------------------------------------------------------ apply
@@ -501,7 +527,7 @@ __global__ void k_fused_sgd_bf16(float* __restrict__ mom,
     mom[i] = m;
     float u = -lr * m;
     float old = atomicAdd(values + i, u);
-    shadow[i] = f32_to_bf16(old + u);
+    shadow[i] = f32_to_bf16(add_uncontracted(old, u));
     if (d1) DP::atomic_add(d1, i, u);
     if (d2) DP::atomic_add(d2, i, u);
     if (d3) DP::atomic_add(d3, i, u);
@@ -695,7 +721,7 @@ __global__ void k_fused_adamw(float* __restrict__ mom, float* __restrict__ vel,
                                 __HIP_MEMORY_SCOPE_AGENT);
     float u = -lr * (m * inv_bc1 / (sqrtf(v * inv_bc2) + eps) + wd * w);
     float old = atomicAdd(values + i, u);
-    if (shadow) shadow[i] = f32_to_bf16(old + u);
+    if (shadow) shadow[i] = f32_to_bf16(add_uncontracted(old, u));
     if (d1) DP::atomic_add(d1, i, u);
     if (d2) DP::atomic_add(d2, i, u);
     if (d3) DP::atomic_add(d3, i, u);

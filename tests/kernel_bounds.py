@@ -1,5 +1,6 @@
 """fp64 references and derived error bounds for the bf16 model kernels
-(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU).
+(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU) and, at the end
+of the file, for the fused fp32 optimizers (AdamW, SGD momentum).
 
 Reference: the same formula evaluated in fp64 on the bf16 inputs; backward
 references use fp64 statistics, never the kernel's saved mean / rstd.
@@ -433,3 +434,181 @@ def check_rms_wrapper(fused_rms_norm, x, w, dy, family, eps=EPS):
         assert v.dtype == torch.bfloat16 and v.shape == ref[k].shape, k
         assert_bf16(v, ref[k], slack[k], "rms", k, family)
     return got
+
+
+# ------------------------------------------------------- fused optimizers
+#
+# k_fused_adamw / k_fused_sgd* evaluate, per element and in fp32,
+#
+#   m = b1*m0 + (1 - b1)*g
+#   v = b2*v0 + (1 - b2)*g*g
+#   u = -lr * (m*ibc1 / (sqrt(v*ibc2) + eps) + wd*w)          (AdamW)
+#
+#   m = mu*m0 + g;  u = -lr*m                                  (SGD momentum)
+#
+# The references below evaluate the same expressions in fp64 on the fp32
+# values the kernel receives (hyperparameters rounded to fp32 first).  The
+# bounds count the roundings on the path to each term, k of them giving
+# gamma(k) = k*U / (1 - k*U) times the term's magnitude; a rounding that
+# lands below 2^-126 adds at most SUB = 2^-149 instead.  A contracted
+# multiply-add drops one of the counted roundings, so the bound holds with
+# or without contraction.  Division and square root are taken as correctly
+# rounded (the build passes no fast-math flag), one rounding each.
+#
+# fp32 range is part of the reference: a term beyond FLT_MAX is +-inf, as
+# it is in any fp32 evaluation (g = 1e20 makes (1 - b2)*g*g overflow, v is
+# inf and the Adam quotient is 0); so are the products m*ibc1 and v*ibc2.
+# Within the bound of FLT_MAX either outcome is accepted.
+
+FLT_MAX = float(torch.finfo(torch.float32).max)
+SUB = 2.0 ** -149
+
+
+def gamma(k):
+    return k * U / (1 - k * U)
+
+
+def f32(x) -> float:
+    """A python scalar as the kernel receives it."""
+    return float(np.float32(x))
+
+
+def _overflow(t):
+    inf = torch.full_like(t, float("inf")).copysign(t)
+    return torch.where(t.abs() > FLT_MAX, inf, t)
+
+
+def adamw_formula(w, m0, v0, g, lr, b1, b2, eps, wd, ibc1, ibc2,
+                  dtype=torch.float64):
+    """One AdamW step: new m, v and the update u."""
+    w, m0, v0, g = (t.to(dtype) for t in (w, m0, v0, g))
+    lr, b1, b2, eps, wd, ibc1, ibc2 = (
+        torch.tensor(f32(s), dtype=dtype)
+        for s in (lr, b1, b2, eps, wd, ibc1, ibc2))
+    one = torch.tensor(1.0, dtype=dtype)
+    m = b1 * m0 + (one - b1) * g
+    v = b2 * v0 + (one - b2) * g * g
+    if dtype == torch.float64:
+        m, v = _overflow(m), _overflow(v)
+    num, vh = m * ibc1, v * ibc2
+    if dtype == torch.float64:      # the two intermediates that can overflow
+        num, vh = _overflow(num), _overflow(vh)
+    u = -lr * (num / (torch.sqrt(vh) + eps) + wd * w)
+    return {"m": m, "v": v, "u": u}
+
+
+def adamw_slack(w, m0, v0, g, lr, b1, b2, eps, wd, ibc1, ibc2):
+    w, m0, v0, g = (t.double() for t in (w, m0, v0, g))
+    lr, b1, b2, eps, wd, ibc1, ibc2 = (
+        f32(s) for s in (lr, b1, b2, eps, wd, ibc1, ibc2))
+    ref = adamw_formula(w, m0, v0, g, lr, b1, b2, eps, wd, ibc1, ibc2)
+    m, v = ref["m"], ref["v"]
+    # m: b1*m0 is rounded as a product and in the sum; (1 - b1)*g also in
+    # the subtraction
+    dm = (gamma(2) * (b1 * m0).abs() + gamma(3) * ((1 - b1) * g).abs()
+          + 3 * SUB)
+    # v: (1 - b2), *g, *g and the sum
+    dv = (gamma(2) * (b2 * v0).abs() + gamma(4) * ((1 - b2) * g * g).abs()
+          + 4 * SUB)
+    num = _overflow(m * ibc1)
+    dnum = ibc1 * dm + gamma(1) * num.abs() + SUB
+    vh = _overflow(v * ibc2)
+    dvh = ibc2 * dv + gamma(1) * vh.abs() + SUB
+    s = torch.sqrt(vh)
+    # |sqrt(a + d) - sqrt(a)| = |d| / (sqrt(a + d) + sqrt(a))
+    #                        <= min(|d| / sqrt(a), sqrt(|d|))
+    ds = torch.minimum(dvh / s.clamp_min(1e-300), torch.sqrt(dvh))
+    ds = ds + gamma(1) * s
+    den = s + eps
+    dden = ds + gamma(1) * den
+    den_lo = (den - dden).clamp_min(1e-300)
+    q = num / den
+    dq = dnum / den_lo + num.abs() * dden / (den * den_lo) + gamma(1) * q.abs()
+    dw = wd * w
+    ddw = gamma(1) * dw.abs() + SUB
+    dsum = dq + ddw + gamma(1) * (q.abs() + dw.abs() + dq + ddw)
+    u = ref["u"]
+    du = lr * dsum + gamma(1) * (u.abs() + lr * dsum) + SUB
+    # v or v*ibc2 = inf: the quotient is exactly 0 and only wd*w remains
+    vinf = torch.isinf(vh) & torch.isfinite(num)
+    du_inf = lr * ddw + gamma(2) * (lr * dw).abs() + SUB
+    du = torch.where(vinf, du_inf, du)
+    dv = torch.where(torch.isinf(v), torch.zeros_like(dv), dv)
+    return {"m": dm, "v": dv, "u": du}
+
+
+def sgd_formula(m0, g, lr, mu, dtype=torch.float64):
+    """One SGD-momentum step: new m and the update u."""
+    m0, g = m0.to(dtype), g.to(dtype)
+    lr, mu = (torch.tensor(f32(s), dtype=dtype) for s in (lr, mu))
+    m = mu * m0 + g
+    if dtype == torch.float64:
+        m = _overflow(m)
+    return {"m": m, "u": -lr * m}
+
+
+def sgd_slack(m0, g, lr, mu):
+    m0, g = m0.double(), g.double()
+    lr, mu = f32(lr), f32(mu)
+    # the product and the sum round mu*m0, the sum alone rounds g
+    dm = gamma(2) * (mu * m0).abs() + gamma(1) * g.abs() + 2 * SUB
+    m = mu * m0 + g
+    du = lr * dm + gamma(1) * (lr * (m.abs() + dm)) + SUB
+    return {"m": dm, "u": du}
+
+
+def assert_within(got, ref, slack, op, out, family):
+    """fp32 output whose final rounding the slack already counts.  Finite
+    references: |got - ref| <= slack.  Infinite: the same infinity.  NaN:
+    NaN.  Within the slack of FLT_MAX: the bound or the infinity."""
+    got, ref, slack = got.double(), ref.double(), slack.double()
+    err = (got - ref).abs()
+    fin = torch.isfinite(ref)
+    ok = fin & (err <= slack)
+    inf = torch.full_like(ref, float("inf")).copysign(ref)
+    ok |= fin & (ref.abs() + slack >= FLT_MAX) & (got == inf)
+    ok |= torch.isinf(ref) & (got == ref)
+    ok |= torch.isnan(ref) & torch.isnan(got)
+    judged = fin & torch.isfinite(got) & (slack > 0)
+    worst = float((err / slack)[judged].max()) if judged.any() else 0.0
+    report(op, out, family, worst, unit="of-bound")
+    if not ok.all():
+        bad = ~ok
+        i = int(bad.flatten().nonzero()[0])
+        raise AssertionError(
+            f"{op} {out} [{family}]: {int(bad.sum())} of {bad.numel()} outside "
+            f"the bound; first at {i}: got {float(got.flatten()[i])!r}, ref "
+            f"{float(ref.flatten()[i])!r}, bound {float(slack.flatten()[i]):.3g}")
+    return worst
+
+
+OPTIM_FAMILIES = ["randn", "zero_g_zero_state", "g_huge", "g_tiny", "wd0"]
+
+
+def optim_inputs(family, n, seed=0):
+    """fp32 w, m0, v0 (>= 0), g and the weight decay of the family."""
+    gen = torch.Generator().manual_seed(77 * seed + n)
+    w = torch.randn(n, generator=gen)
+    m0 = torch.randn(n, generator=gen)
+    v0 = torch.randn(n, generator=gen) ** 2
+    g = torch.randn(n, generator=gen)
+    sign = torch.where(torch.arange(n) % 2 == 0, 1.0, -1.0)
+    wd = 0.01
+    if family == "zero_g_zero_state":
+        g, m0, v0 = torch.zeros(n), torch.zeros(n), torch.zeros(n)
+    elif family == "g_huge":
+        g = 1e20 * sign
+    elif family == "g_tiny":
+        g = 1e-30 * sign
+    elif family == "wd0":
+        wd = 0.0
+    elif family != "randn":
+        raise ValueError(family)
+    return w, m0, v0, g, wd
+
+
+def bias_corrections(b1, b2, step):
+    """1 / (1 - beta^step) in fp32, as Engine::fused_adamw computes them."""
+    f = np.float32
+    return (float(f(1) / (f(1) - np.power(f(b1), f(step)))),
+            float(f(1) / (f(1) - np.power(f(b2), f(step)))))

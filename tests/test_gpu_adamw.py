@@ -63,8 +63,8 @@ def test_bf16_grads_shadow():
                                      EPS, WD)
         torch.cuda.synchronize()
         torch.testing.assert_close(sh.values, ref, rtol=1e-5, atol=1e-6)
-        # shadow is the bf16 rounding of the fp32 master
-        torch.testing.assert_close(shadow.float(), sh.values, rtol=1e-2,
-                                   atol=1e-2)
+        # shadow is exactly the bf16 rounding of the fp32 master
+        assert torch.equal(shadow.view(torch.int16),
+                           sh.values.to(torch.bfloat16).view(torch.int16))
     finally:
         sh.close()

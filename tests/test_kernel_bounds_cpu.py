@@ -184,3 +184,92 @@ def test_exact_sum_inputs_are_exact():
         for r in x.float()[perm].numpy():
             acc = acc + r
         assert np.array_equal(acc.astype(np.float64), ref.numpy())
+
+
+# ------------------------------------------------------- fused optimizers
+
+LR, B1, B2, MU = 2e-2, 0.9, 0.95, 0.9
+
+
+def _adamw_args(family, eps, step, n=1003, g=None):
+    w, m0, v0, g0, wd = kb.optim_inputs(family, n)
+    i1, i2 = kb.bias_corrections(B1, B2, step)
+    return (w, m0, v0, g0 if g is None else g, LR, B1, B2, eps, wd, i1, i2)
+
+
+@pytest.mark.parametrize("step", [1, 10000])
+@pytest.mark.parametrize("eps", [1e-8, 1e-6])
+@pytest.mark.parametrize("family", kb.OPTIM_FAMILIES)
+def test_fp32_reference_meets_bound_adamw(family, eps, step):
+    args = _adamw_args(family, eps, step)
+    ref = kb.adamw_formula(*args)
+    f32 = kb.adamw_formula(*args, dtype=torch.float32)
+    slack = kb.adamw_slack(*args)
+    for k in ("m", "v", "u"):
+        assert f32[k].dtype == torch.float32
+        kb.assert_within(f32[k], ref[k], slack[k], "adamw-fp32cpu", k,
+                         f"{family}/eps={eps:g}/step={step}")
+    if family == "g_huge":          # fp32 range is part of the reference
+        assert torch.isinf(ref["v"]).all() and torch.isfinite(ref["u"]).all()
+    if family == "zero_g_zero_state":
+        wd = args[8]
+        assert torch.equal(ref["u"], -kb.f32(LR) * (kb.f32(wd) * args[0].double()))
+
+
+@pytest.mark.parametrize("step", [1, 10000])
+def test_fp32_reference_meets_bound_adamw_all_bf16(step):
+    g = kb.all_bf16().float()
+    args = _adamw_args("randn", 1e-8, step, n=g.numel(), g=g)
+    ref = kb.adamw_formula(*args)
+    f32 = kb.adamw_formula(*args, dtype=torch.float32)
+    slack = kb.adamw_slack(*args)
+    fin = torch.isfinite(g)
+    for k in ("m", "v", "u"):
+        assert not torch.isfinite(ref[k][~fin]).any()
+        assert not torch.isfinite(f32[k][~fin]).any()
+        kb.assert_within(f32[k][fin], ref[k][fin], slack[k][fin],
+                         "adamw-fp32cpu", k, f"all-bf16/step={step}")
+
+
+def test_bias_corrections():
+    i1, i2 = kb.bias_corrections(B1, B2, 1)
+    assert abs(i1 - 10.0) < 1e-5 and abs(i2 - 20.0) < 1e-4
+    i1, i2 = kb.bias_corrections(B1, B2, 10000)
+    assert i1 == 1.0 and i2 == 1.0
+
+
+def test_adamw_bound_rejects_wrong_formulas():
+    """Decay against the updated weight, a dropped bias correction, a 1e-6
+    relative error in m: each leaves the bound."""
+    args = list(_adamw_args("zero_g_zero_state", 1e-8, 1))
+    ref = kb.adamw_formula(*args)
+    slack = kb.adamw_slack(*args)
+    w, wd = args[0].double(), kb.f32(args[8])
+    u_post = -kb.f32(LR) * wd * (w + ref["u"])      # decay on w + u
+    assert ((u_post - ref["u"]).abs() > slack["u"]).sum() > 900
+    args = list(_adamw_args("randn", 1e-8, 1))
+    ref = kb.adamw_formula(*args)
+    slack = kb.adamw_slack(*args)
+    no_bc2 = kb.adamw_formula(*args[:10], 1.0)
+    assert ((no_bc2["u"] - ref["u"]).abs() > slack["u"]).sum() > 900
+    with pytest.raises(AssertionError):
+        kb.assert_within(ref["m"] * (1 + 1e-6), ref["m"], slack["m"], "adamw",
+                         "m", "perturbed")
+
+
+@pytest.mark.parametrize("g16", [False, True])
+def test_fp32_reference_meets_bound_sgd(g16):
+    n = 65536
+    _, m0, _, g, _ = kb.optim_inputs("randn", n)
+    if g16:
+        g = kb.all_bf16().float()
+    ref = kb.sgd_formula(m0, g, LR, MU)
+    f32 = kb.sgd_formula(m0, g, LR, MU, dtype=torch.float32)
+    slack = kb.sgd_slack(m0, g, LR, MU)
+    fin = torch.isfinite(g)
+    for k in ("m", "u"):
+        kb.assert_within(f32[k][fin], ref[k][fin], slack[k][fin],
+                         "sgd-fp32cpu", k, "all-bf16" if g16 else "randn")
+    with pytest.raises(AssertionError):
+        kb.assert_within(ref["u"][fin] * (1 + 1e-6), ref["u"][fin],
+                         slack["u"][fin], "sgd", "u", "perturbed")
