@@ -2,7 +2,8 @@
 """Microbenchmark the model-side fused kernels (LN, add+LN, GELU, RMSNorm,
 add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
 GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
-section alone, `--only-add-rms` the add+RMSNorm section."""
+section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
+the fused bias-gradient section."""
 import json
 import sys
 import time
@@ -113,12 +114,66 @@ def bench_add_rms(out):
         out[f"unfused_add_rms{C}_bwd_tbps"] = round(4 * A / ms / 1e9, 2)
 
 
+def bench_bias_grad(out):
+    # ---- bias gradients fused into GELU backward and the qkv gradient pack
+    # (GPT-2-small B=64: R=65536, fc C=3072, qkv 3 x 768) against the torch
+    # kernels they replace.  Both sides include the bias reduce.  Effective
+    # TB/s from the mandatory bytes: GELU backward reads dy and x and writes
+    # dx (3A); the pack reads and writes 3 x (R, 768) (2A').
+    s = torch.cuda.current_stream().cuda_stream
+    R, C = 65536, 3072
+    x = (torch.randn(R, C, device="cuda") * 2).to(torch.bfloat16)
+    dy = torch.randn(R, C, device="cuda").to(torch.bfloat16)
+    dx = torch.empty_like(x)
+    db = torch.empty(C, dtype=torch.bfloat16, device="cuda")
+    part = torch.empty(_core.bias_grad_partial_floats(C),
+                       dtype=torch.float32, device="cuda")
+    ms = t(lambda: _core.gelu_bwd_colsum(
+        dy.data_ptr(), x.data_ptr(), dx.data_ptr(), db.data_ptr(),
+        part.data_ptr(), R, C, s), iters=30)
+    out["gelu_bwd_colsum_ms"] = round(ms, 4)
+    out["gelu_bwd_colsum_tbps"] = round(3 * x.numel() * 2 / ms / 1e9, 2)
+    xt = x.clone().requires_grad_(True)
+    yt = torch.nn.functional.gelu(xt, approximate="tanh")
+
+    def torch_gelu_bwd():
+        (g,) = torch.autograd.grad(yt, xt, dy, retain_graph=True)
+        return g.sum(0)
+    ms = t(torch_gelu_bwd, iters=30)
+    out["torch_gelu_bwd_plus_reduce_ms"] = round(ms, 4)
+    out["torch_gelu_bwd_plus_reduce_tbps"] = round(
+        3 * x.numel() * 2 / ms / 1e9, 2)
+
+    Cq = 768
+    srcs = [torch.randn(R, Cq, device="cuda").to(torch.bfloat16)
+            for _ in range(3)]
+    dst = torch.empty(R, 3 * Cq, dtype=torch.bfloat16, device="cuda")
+    dbq = torch.empty(3 * Cq, dtype=torch.bfloat16, device="cuda")
+    ms = t(lambda: _core.pack3_colsum(
+        srcs[0].data_ptr(), srcs[1].data_ptr(), srcs[2].data_ptr(),
+        dst.data_ptr(), dbq.data_ptr(), part.data_ptr(), R, Cq, s), iters=30)
+    out["pack3_colsum_ms"] = round(ms, 4)
+    out["pack3_colsum_tbps"] = round(2 * dst.numel() * 2 / ms / 1e9, 2)
+    ms = t(lambda: torch.cat(srcs, dim=1).sum(0), iters=30)
+    out["torch_cat_plus_reduce_ms"] = round(ms, 4)
+    out["torch_cat_plus_reduce_tbps"] = round(
+        2 * dst.numel() * 2 / ms / 1e9, 2)
+    # the parts on their own, for the README
+    out["torch_cat_ms"] = round(t(lambda: torch.cat(srcs, dim=1), iters=30), 4)
+    out["torch_reduce2304_ms"] = round(t(lambda: dst.sum(0), iters=30), 4)
+    out["torch_reduce3072_ms"] = round(t(lambda: dx.sum(0), iters=30), 4)
+
+
 def main():
     torch.cuda.set_device(0)
     s = torch.cuda.current_stream().cuda_stream
     out = {}
     if "--only-rope" in sys.argv[1:]:
         bench_rope(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-bias-grad" in sys.argv[1:]:
+        bench_bias_grad(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-add-rms" in sys.argv[1:]:
@@ -279,6 +334,7 @@ def main():
 
     bench_rope(out)
     bench_add_rms(out)
+    bench_bias_grad(out)
 
     # ---- CE (R=65536, V=50257) ----
     R, V = 65536, 50257

@@ -30,12 +30,13 @@ SOURCES = [
     "add_rms_kernels.hip",
     "ce_kernels.hip",
     "gelu_kernels.hip",
+    "bias_grad_kernels.hip",
     "swiglu_kernels.hip",
     "rope_kernels.hip",
     "bindings.cpp",
 ]
 
-HEADERS = ["common.h", "codec_cpu.h", "engine.h", "hip_api.h", "rccl_transport.h"]
+HEADERS = ["common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "rccl_transport.h"]
 
 
 def pybind11_include():

@@ -329,6 +329,31 @@ PYBIND11_MODULE(_core, m) {
                  reinterpret_cast<hipStream_t>(stream));
   });
 
+  // bias gradients fused into GELU backward / the qkv gradient pack
+  m.def("bias_grad_partial_floats", &hip_bias_grad_partial_floats);
+  m.def("bias_grad_sweep_rows", &hip_bias_grad_sweep_rows);
+  m.def("gelu_bwd_colsum", [](uintptr_t dy, uintptr_t x, uintptr_t dx,
+                              uintptr_t db, uintptr_t partial, int64_t R,
+                              int64_t C, uintptr_t stream) {
+    hip_gelu_bwd_colsum(reinterpret_cast<const void*>(dy),
+                        reinterpret_cast<const void*>(x),
+                        reinterpret_cast<void*>(dx),
+                        reinterpret_cast<void*>(db),
+                        reinterpret_cast<float*>(partial), R, C,
+                        reinterpret_cast<hipStream_t>(stream));
+  });
+  m.def("pack3_colsum", [](uintptr_t s0, uintptr_t s1, uintptr_t s2,
+                           uintptr_t dst, uintptr_t db, uintptr_t partial,
+                           int64_t R, int64_t C, uintptr_t stream) {
+    hip_pack3_colsum(reinterpret_cast<const void*>(s0),
+                     reinterpret_cast<const void*>(s1),
+                     reinterpret_cast<const void*>(s2),
+                     reinterpret_cast<void*>(dst),
+                     reinterpret_cast<void*>(db),
+                     reinterpret_cast<float*>(partial), R, C,
+                     reinterpret_cast<hipStream_t>(stream));
+  });
+
   // fused bf16 cross-entropy
   m.def("ce_fwd", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,
                      uintptr_t row_m, uintptr_t row_lse, int64_t R, int64_t V,

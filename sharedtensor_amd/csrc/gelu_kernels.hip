@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "gelu_math.h"
 #include "hip_api.h"
 
 namespace shamd {
@@ -18,47 +19,6 @@ namespace shamd {
       throw std::runtime_error(std::string("HIP error: ") +                \
                                hipGetErrorString(_e));                     \
   } while (0)
-
-static __device__ __forceinline__ float gl_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float gl_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint16_t gl_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-static __device__ __forceinline__ uint32_t gl_pack(float lo, float hi) {
-  return static_cast<uint32_t>(gl_bf16(lo)) |
-         (static_cast<uint32_t>(gl_bf16(hi)) << 16);
-}
-
-// gelu(x) = 0.5 x (1 + tanh(k (x + 0.044715 x^3))), k = sqrt(2/pi)
-constexpr float GK = 0.7978845608028654f;
-constexpr float GC = 0.044715f;
-
-static __device__ __forceinline__ float gelu_f(float x) {
-  float inner = GK * (x + GC * x * x * x);
-  return 0.5f * x * (1.f + tanhf(inner));
-}
-
-// gelu'(x) is 1 or 0 to well below fp32 resolution for |x| >= 10, so the
-// formula is evaluated at x clamped to [-10, 10]: unclamped, x * x reaches
-// inf for |x| > 1.8e19 and sech2 == 0 then meets it as 0 * inf = NaN.  NaN
-// passes through the clamp (fminf/fmaxf return the other operand, so the
-// NaN is put back by hand).
-static __device__ __forceinline__ float gelu_grad_f(float xin) {
-  float x = fminf(fmaxf(xin, -10.f), 10.f);
-  if (xin != xin) x = xin;
-  float x2 = x * x;
-  float inner = GK * x * (1.f + GC * x2);
-  float t = tanhf(inner);
-  float sech2 = 1.f - t * t;
-  return 0.5f * (1.f + t) + 0.5f * x * sech2 * GK * (1.f + 3.f * GC * x2);
-}
 
 // uint4 (8 bf16) per iteration — the pair-only variant measured SLOWER
 // than torch's 8-wide elementwise kernels in round 1; round 2's SwiGLU

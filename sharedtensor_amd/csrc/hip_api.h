@@ -205,10 +205,30 @@ void hip_rope_qk(const void* q, const void* k, void* q_out, void* k_out,
                  const RopeStrides& k_in, const RopeStrides& q_os,
                  const RopeStrides& k_os, bool inverse, hipStream_t s);
 
-// Fused bf16 GELU-tanh (gelu_kernels.hip); n must be even, buffers
-// 4-byte aligned (pair loads).
+// Fused bf16 GELU-tanh (gelu_kernels.hip); n must be a multiple of 8,
+// buffers 16-byte aligned (uint4 loads).
 void hip_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s);
 void hip_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n,
                   hipStream_t s);
+
+// Bias gradients fused into the pass before them (bias_grad_kernels.hip).
+// All tensors bf16 and 16-byte aligned, C a multiple of 8, R > 0; both throw
+// otherwise.  `db` receives the bf16 column sums (fp32 accumulation of the
+// bf16 values written, fixed order, no atomics); `partial` is fp32 scratch of
+// hip_bias_grad_partial_floats(columns of the output) and needs no zeroing.
+//   gelu_bwd_colsum: dx = bf16(dy * gelu'(x)) as hip_gelu_bwd, db[C] = column
+//                    sums of dx.
+//   pack3_colsum:    dst (R, 3C) = [s0 | s1 | s2], each (R, C) with row
+//                    stride C; db[3C] = column sums of dst.
+// hip_bias_grad_sweep_rows: rows one iteration of the grid's row loop covers
+// for an (R, N) output of the GELU kernel or, with `pack`, of the pack kernel
+// (tests size their grid-stride cases with it).
+int64_t hip_bias_grad_partial_floats(int64_t N);
+int64_t hip_bias_grad_sweep_rows(int64_t R, int64_t N, bool pack);
+void hip_gelu_bwd_colsum(const void* dy, const void* x, void* dx, void* db,
+                         float* partial, int64_t R, int64_t C, hipStream_t s);
+void hip_pack3_colsum(const void* s0, const void* s1, const void* s2,
+                      void* dst, void* db, float* partial, int64_t R,
+                      int64_t C, hipStream_t s);
 
 }  // namespace shamd

@@ -11,6 +11,7 @@ runs in our HIP kernels underneath it.
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 
 import torch
@@ -44,6 +45,31 @@ class GPT2Config:
 # noise (profiles/r03/bench_ln_fusion_ab.json); False restores the GEMM
 # epilogue bias.
 FUSE_PROJ_BIAS = True
+
+# Take qkv.bias.grad inside the pack of dq/dk/dv and fc.bias.grad inside GELU
+# backward (ops/fused_bias_grad.py): the forward GEMMs keep their bias, only
+# the route of its gradient changes.  The qkv half measured 0.124 ms against
+# 0.283 ms for torch's cat + reduce and is on.  The GELU half measured
+# 0.378 ms against 0.356 ms for GeluBackward + reduce (profiles/r07/), so it
+# stays off: a tested alternative, like ops/fused_gelu.py.
+# SHTENS_FUSED_QKV_BGRAD / SHTENS_FUSED_GELU_BGRAD = 0 or 1 override either
+# flag for an A/B run.
+FUSE_QKV_BIAS_GRAD = True
+FUSE_FC_BIAS_GRAD = False
+
+
+def _flag(env: str, default: bool) -> bool:
+    v = os.environ.get(env)
+    return default if v is None else v == "1"
+
+
+def _bias_grad_ok(flag: bool, which: str, x, lin: nn.Linear) -> bool:
+    if not (flag and x.is_cuda and x.dtype == torch.bfloat16
+            and lin.bias is not None and torch.is_grad_enabled()):
+        return False
+    from ..ops import fused_bias_grad as fb
+    check = fb.can_use_gelu if which == "gelu" else fb.can_use_qkv
+    return check(x, lin.weight, lin.bias)
 
 
 class FusedLayerNorm(nn.LayerNorm):
@@ -110,7 +136,13 @@ class CausalSelfAttention(nn.Module):
 
     def forward(self, x, proj_bias=True):
         B, T, C = x.shape
-        q, k, v = self.qkv(x).split(C, dim=2)
+        if _bias_grad_ok(_flag("SHTENS_FUSED_QKV_BGRAD", FUSE_QKV_BIAS_GRAD),
+                         "qkv", x, self.qkv):
+            from ..ops import fused_bias_grad
+            qkv = F.linear(x, self.qkv.weight, self.qkv.bias.detach())
+            q, k, v = fused_bias_grad.qkv_split_bgrad(qkv, self.qkv.bias)
+        else:
+            q, k, v = self.qkv(x).split(C, dim=2)
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
@@ -139,10 +171,16 @@ class MLP(nn.Module):
         self.proj = nn.Linear(4 * cfg.n_embd, cfg.n_embd)
 
     def forward(self, x, proj_bias=True):
-        # torch's gelu measured FASTER than our fused kernel here (0.187 vs
-        # 0.251 ms fwd on the B=64 shape; ops/fused_gelu.py kept as a
+        # torch's gelu forward ties our fused kernel here (0.194 vs 0.195 ms
+        # on the B=64 shape, profiles/README.md; ops/fused_gelu.py kept as a
         # measured alternative) — keep the library kernel
-        h = F.gelu(self.fc(x), approximate="tanh")
+        if _bias_grad_ok(_flag("SHTENS_FUSED_GELU_BGRAD", FUSE_FC_BIAS_GRAD),
+                         "gelu", x, self.fc):
+            from ..ops import fused_bias_grad
+            pre = F.linear(x, self.fc.weight, self.fc.bias.detach())
+            h = fused_bias_grad.bias_gelu_bgrad(pre, self.fc.bias)
+        else:
+            h = F.gelu(self.fc(x), approximate="tanh")
         if not proj_bias:  # the caller adds proj.bias (see Block)
             return F.linear(h, self.proj.weight)
         return self.proj(h)

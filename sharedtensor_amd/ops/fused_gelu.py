@@ -1,8 +1,11 @@
 """Fused bf16 GELU-tanh (hand-written CDNA4 kernels, csrc/gelu_kernels.hip).
 
-Measured SLOWER than torch's gelu forward on MI355X (0.251 vs 0.187 ms at
-(65536, 3072); backward ties) — torch's 8-wide vectorized elementwise wins.
-Kept as a correct, tested alternative; NOT wired into the models."""
+uint4 (8 x bf16) accesses reach parity with torch's gelu forward on MI355X
+(0.195 vs 0.194 ms at (65536, 3072), both at the elementwise bandwidth limit;
+round 1's pair-load variant was 26% slower — profiles/README.md), so there is
+nothing to gain: kept as a correct, tested alternative, NOT wired into the
+models.  k_gelu_bwd_colsum (ops/fused_bias_grad.py, off by default) shares
+gelu_grad_f with the backward kernel here."""
 from __future__ import annotations
 
 import torch
