@@ -25,6 +25,7 @@ SOURCES = [
     "engine.cpp",
     "rccl_transport.cpp",
     "hip_kernels.hip",
+    "grad_clip_kernels.hip",
     "ln_kernels.hip",
     "add_ln_kernels.hip",
     "add_rms_kernels.hip",

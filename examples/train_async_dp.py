@@ -38,7 +38,8 @@ def rank_main(args):
         lr=args.lr, optimizer=args.opt,
         amp_dtype=torch.bfloat16 if dev.type == "cuda" else None,
         param_dtype=torch.bfloat16 if dev.type == "cuda" else torch.float32,
-        codec=args.codec, sync_interval_s=0.05, snapshot_join=True)
+        codec=args.codec, sync_interval_s=0.05, snapshot_join=True,
+        max_grad_norm=args.max_grad_norm)
     B, T = (8, cfg.block_size) if dev.type == "cuda" else (2, 32)
     gen = torch.Generator().manual_seed(rank)
     data = torch.randint(0, cfg.vocab_size, (B, T + 1), generator=gen).to(dev)
@@ -47,9 +48,13 @@ def rank_main(args):
         loss = trainer.step(data[:, :-1], data[:, 1:])
         if step % 10 == 0 or step == args.steps - 1:
             s = trainer.stats()
+            gs = trainer.grad_stats()  # None unless --max-grad-norm is set
+            clip = "" if gs is None else (
+                f" gnorm {gs['grad_norm']:.3g} coef {gs['clip_coef']:.3g} "
+                f"skipped {gs['skipped_steps']}")
             print(f"[rank {rank}] step {step:4d} loss {float(loss):.3f} "
                   f"sync_rounds {s['rounds_sent']} "
-                  f"stale {s['staleness_p50']}", flush=True)
+                  f"stale {s['staleness_p50']}{clip}", flush=True)
     print(f"[rank {rank}] {B * T * args.steps / (time.time() - t0):,.0f} "
           f"tokens/s", flush=True)
     trainer.close()
@@ -63,6 +68,10 @@ def main():
     ap.add_argument("--opt", choices=["sgd", "adamw"], default="sgd")
     ap.add_argument("--codec", choices=["1bit", "fp8", "int4"], default="1bit")
     ap.add_argument("--port", type=int, default=22000)
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip each rank's gradient to this global L2 norm "
+                         "inside the fused optimizer step; a step with an "
+                         "inf/NaN gradient is skipped (default: off)")
     args = ap.parse_args()
     if "RANK" in os.environ:
         rank_main(args)

@@ -127,7 +127,7 @@ void py_gpu_add_scatter(uintptr_t src, int64_t n, double alpha,
 // dsts[0] = fp32 values (or 0); dsts[1..3] = delta-typed
 void py_gpu_fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double mu,
                       int64_t n, std::vector<uintptr_t> dsts, uintptr_t stream,
-                      bool delta_bf16) {
+                      bool delta_bf16, uintptr_t clip_state) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
   hip_fused_sgd(reinterpret_cast<float*>(mom),
@@ -135,7 +135,8 @@ void py_gpu_fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double mu,
                 static_cast<float>(mu), n, reinterpret_cast<float*>(d[0]),
                 reinterpret_cast<void*>(d[1]), reinterpret_cast<void*>(d[2]),
                 reinterpret_cast<void*>(d[3]), delta_bf16,
-                reinterpret_cast<hipStream_t>(stream));
+                reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<const ClipState*>(clip_state));
 }
 
 // dsts[0] = fp32 values (required: the kernel reads the pre-update weight);
@@ -143,7 +144,8 @@ void py_gpu_fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double mu,
 void py_gpu_fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                            uintptr_t shadow_bf16, double lr, double mu,
                            int64_t n, std::vector<uintptr_t> dsts,
-                           uintptr_t stream, bool delta_bf16) {
+                           uintptr_t stream, bool delta_bf16,
+                           uintptr_t clip_state) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
   if (!d[0] || !shadow_bf16)
@@ -156,7 +158,8 @@ void py_gpu_fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                      reinterpret_cast<void*>(d[1]),
                      reinterpret_cast<void*>(d[2]),
                      reinterpret_cast<void*>(d[3]), delta_bf16,
-                     reinterpret_cast<hipStream_t>(stream));
+                     reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const ClipState*>(clip_state));
 }
 
 // dsts[0] = fp32 values (required); dsts[1..3] = delta-typed.  shadow may be
@@ -167,7 +170,7 @@ void py_gpu_fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                         double beta1, double beta2, double eps, double wd,
                         double inv_bc1, double inv_bc2, int64_t n,
                         std::vector<uintptr_t> dsts, uintptr_t stream,
-                        bool delta_bf16) {
+                        bool delta_bf16, uintptr_t clip_state) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
   if (!d[0]) throw std::runtime_error("gpu_fused_adamw: values required");
@@ -181,7 +184,24 @@ void py_gpu_fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                   reinterpret_cast<float*>(d[0]),
                   reinterpret_cast<void*>(d[1]), reinterpret_cast<void*>(d[2]),
                   reinterpret_cast<void*>(d[3]), delta_bf16,
-                  reinterpret_cast<hipStream_t>(stream));
+                  reinterpret_cast<hipStream_t>(stream),
+                  reinterpret_cast<const ClipState*>(clip_state));
+}
+
+// Exactly one of grad (fp32) and grad_bf16 is non-zero.  scratch: device
+// fp64[>= 2048]; state: 32 device bytes (common.h ClipState), zeroed once by
+// the caller.  ValueError unless max_norm is finite and > 0.
+void py_gpu_grad_clip_coef(uintptr_t grad, uintptr_t grad_bf16, int64_t n,
+                           double max_norm, uintptr_t scratch, uintptr_t state,
+                           uintptr_t stream) {
+  if (!grad == !grad_bf16)
+    throw std::invalid_argument(
+        "gpu_grad_clip_coef: pass exactly one of grad and grad_bf16");
+  hip_grad_clip_coef(reinterpret_cast<const void*>(grad ? grad : grad_bf16),
+                     grad_bf16 != 0, n, max_norm,
+                     reinterpret_cast<double*>(scratch),
+                     reinterpret_cast<ClipState*>(state),
+                     reinterpret_cast<hipStream_t>(stream));
 }
 
 // out := values (fp32), delta -= values (delta-typed)
@@ -245,11 +265,23 @@ PYBIND11_MODULE(_core, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("copy_to", &Engine::copy_to,
            py::call_guard<py::gil_scoped_release>())
-      .def("fused_sgd", &Engine::fused_sgd,
+      .def("fused_sgd", &Engine::fused_sgd, py::arg("mom"), py::arg("grad"),
+           py::arg("lr"), py::arg("momentum"), py::arg("stream"),
+           py::arg("clip_state") = 0,
            py::call_guard<py::gil_scoped_release>())
-      .def("fused_sgd_bf16", &Engine::fused_sgd_bf16,
+      .def("fused_sgd_bf16", &Engine::fused_sgd_bf16, py::arg("mom"),
+           py::arg("grad"), py::arg("shadow"), py::arg("lr"),
+           py::arg("momentum"), py::arg("stream"), py::arg("clip_state") = 0,
            py::call_guard<py::gil_scoped_release>())
-      .def("fused_adamw", &Engine::fused_adamw,
+      .def("fused_adamw", &Engine::fused_adamw, py::arg("mom"),
+           py::arg("vel"), py::arg("grad"), py::arg("grad_bf16"),
+           py::arg("shadow"), py::arg("lr"), py::arg("beta1"),
+           py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("step"),
+           py::arg("stream"), py::arg("clip_state") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("grad_clip_coef", &Engine::grad_clip_coef, py::arg("grad"),
+           py::arg("grad_bf16"), py::arg("n"), py::arg("max_norm"),
+           py::arg("scratch"), py::arg("state"), py::arg("stream"),
            py::call_guard<py::gil_scoped_release>())
       .def("notify_dirty", &Engine::notify_dirty)
       .def("close", &Engine::close, py::call_guard<py::gil_scoped_release>())
@@ -292,17 +324,22 @@ PYBIND11_MODULE(_core, m) {
         py::arg("delta_bf16") = false);
   m.def("gpu_fused_sgd", &py_gpu_fused_sgd, py::arg("mom"), py::arg("grad"),
         py::arg("lr"), py::arg("mu"), py::arg("n"), py::arg("dsts"),
-        py::arg("stream"), py::arg("delta_bf16") = false);
+        py::arg("stream"), py::arg("delta_bf16") = false,
+        py::arg("clip_state") = 0);
   m.def("gpu_fused_sgd_bf16", &py_gpu_fused_sgd_bf16, py::arg("mom"),
         py::arg("grad"), py::arg("shadow"), py::arg("lr"), py::arg("mu"),
         py::arg("n"), py::arg("dsts"), py::arg("stream"),
-        py::arg("delta_bf16") = false);
+        py::arg("delta_bf16") = false, py::arg("clip_state") = 0);
   m.def("gpu_fused_adamw", &py_gpu_fused_adamw, py::arg("mom"),
         py::arg("vel"), py::arg("grad"), py::arg("grad_bf16"),
         py::arg("shadow"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("wd"), py::arg("inv_bc1"), py::arg("inv_bc2"),
         py::arg("n"), py::arg("dsts"), py::arg("stream"),
-        py::arg("delta_bf16") = false);
+        py::arg("delta_bf16") = false, py::arg("clip_state") = 0);
+  m.def("gpu_grad_clip_coef", &py_gpu_grad_clip_coef, py::arg("grad"),
+        py::arg("grad_bf16"), py::arg("n"), py::arg("max_norm"),
+        py::arg("scratch"), py::arg("state"), py::arg("stream"));
+  m.attr("GRAD_CLIP_MAX_BLOCKS") = GRAD_CLIP_MAX_BLOCKS;
   m.def("gpu_snapshot_capture", &py_gpu_snapshot_capture, py::arg("values"),
         py::arg("delta"), py::arg("out"), py::arg("n"), py::arg("stream"),
         py::arg("delta_bf16") = false);

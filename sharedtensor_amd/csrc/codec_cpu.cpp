@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 #include <thread>
 #include <vector>
 
@@ -52,6 +53,41 @@ void cpu_pfor(int64_t n, const std::function<void(int64_t, int64_t)>& fn) {
   for (int i = 1; i < nt; ++i) ths.emplace_back(worker);
   worker();
   for (auto& t : ths) t.join();
+}
+
+// ------------------------------------------------------------ gradient clip
+void cpu_grad_clip_coef(const float* grad, int64_t n, double max_norm,
+                        ClipState* st) {
+  if (!(max_norm > 0.0) || std::isinf(max_norm))
+    throw std::invalid_argument("grad_clip_coef: max_norm must be finite and > 0");
+  if (n < 1) throw std::invalid_argument("grad_clip_coef: n must be >= 1");
+  if (!grad || !st) throw std::invalid_argument("grad_clip_coef: null pointer");
+  int64_t nchunks = (n + PF_CHUNK - 1) / PF_CHUNK;
+  std::vector<double> part(static_cast<size_t>(nchunks), 0.0);
+  // cpu_pfor hands a single worker the whole range: walk it in the same
+  // fixed chunks, so the partials do not depend on the thread count
+  cpu_pfor(n, [&](int64_t lo, int64_t hi) {
+    for (int64_t c0 = lo; c0 < hi; c0 += PF_CHUNK) {
+      int64_t c1 = c0 + PF_CHUNK < hi ? c0 + PF_CHUNK : hi;
+      double ss = 0.0;
+      for (int64_t i = c0; i < c1; ++i) {
+        double d = grad[i];
+        ss += d * d;
+      }
+      part[static_cast<size_t>(c0 / PF_CHUNK)] = ss;
+    }
+  });
+  double sumsq = 0.0;
+  for (double p : part) sumsq += p;
+  const double nrm = std::sqrt(sumsq);
+  const bool bad = !std::isfinite(sumsq);
+  double c = max_norm / (nrm + 1e-6);
+  if (c > 1.0) c = 1.0;
+  st->sumsq = sumsq;
+  st->norm = static_cast<float>(nrm);
+  st->coef = bad ? 0.0f : static_cast<float>(c);
+  st->skip = bad ? 1u : 0u;
+  if (bad) st->skipped_total += 1u;
 }
 
 // ----------------------------------------------------------------- fp8 e4m3

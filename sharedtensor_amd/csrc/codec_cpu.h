@@ -43,6 +43,19 @@ inline float atomic_load_f32(const float* p) {
 // where the CPU engine beats it by an order of magnitude on big tensors.
 void cpu_pfor(int64_t n, const std::function<void(int64_t, int64_t)>& fn);
 
+// Host twin of hip_grad_clip_coef: fp64 sum of squares over the fixed
+// cpu_pfor chunks, chunk partials summed in index order (the result does not
+// depend on the thread count), then the same ClipState in host memory.
+// Throws std::invalid_argument unless max_norm is finite and > 0.
+void cpu_grad_clip_coef(const float* grad, int64_t n, double max_norm,
+                        ClipState* st);
+
+// g * coef rounded to fp32 on its own, as the HIP kernels do it.
+inline float mul_uncontracted_f32(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // OCP fp8 e4m3fn conversions (shared semantics with torch.float8_e4m3fn;
 // round-to-nearest-even, caller pre-clamps to +-448).
 uint8_t f32_to_e4m3(float x);

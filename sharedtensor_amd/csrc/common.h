@@ -97,6 +97,24 @@ struct LinkStatsSnap {
   bool rccl;
 };
 
+// Gradient-clipping state: written by grad_clip_coef (device memory for GPU
+// engines, host memory for CPU engines) and read by the fused optimizer
+// steps.  The layout is public: python reads it back as 8 int32 words.
+struct ClipState {
+  double sumsq;            // sum of g*g in fp64
+  float norm;              // (float)sqrt(sumsq); may be inf
+  float coef;              // (float)min(1, max_norm / (sqrt(sumsq) + 1e-6));
+                           // 0 when skip is set
+  uint32_t skip;           // 1: sumsq is not finite, the step must not run
+  uint32_t skipped_total;  // running count of skip == 1, never reset here
+  uint32_t pad[2];
+};
+static_assert(sizeof(ClipState) == 32, "clip state layout is public");
+
+// Partials of the sum-of-squares reduction: callers size the fp64 scratch
+// for this many blocks.
+constexpr int GRAD_CLIP_MAX_BLOCKS = 2048;
+
 constexpr uint32_t MAGIC = 0x53544132;  // "STA2"
 constexpr uint16_t PROTO_VERSION = 2;
 

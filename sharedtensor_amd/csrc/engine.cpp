@@ -1732,8 +1732,26 @@ void Engine::copy_to(uintptr_t dst, int64_t n, uintptr_t stream) {
   }
 }
 
+void Engine::grad_clip_coef(uintptr_t grad, bool grad_bf16, int64_t n,
+                            double max_norm, uintptr_t scratch,
+                            uintptr_t state, uintptr_t stream) {
+  if (n != n_) throw std::runtime_error("grad_clip_coef: size mismatch");
+  if (gpu()) {
+    hip_grad_clip_coef(reinterpret_cast<const void*>(grad), grad_bf16, n,
+                       max_norm, reinterpret_cast<double*>(scratch),
+                       reinterpret_cast<ClipState*>(state),
+                       reinterpret_cast<hipStream_t>(stream));
+  } else {
+    if (grad_bf16) throw std::runtime_error("bf16 grads are a GPU-only path");
+    cpu_grad_clip_coef(reinterpret_cast<const float*>(grad), n, max_norm,
+                       reinterpret_cast<ClipState*>(state));
+  }
+}
+
 void Engine::fused_sgd(uintptr_t mom, uintptr_t grad, double lr,
-                       double momentum, uintptr_t stream) {
+                       double momentum, uintptr_t stream,
+                       uintptr_t clip_state) {
+  const ClipState* clip = reinterpret_cast<const ClipState*>(clip_state);
   std::shared_lock<std::shared_mutex> ug(user_m_);
   void* d[3];
   for (int i = 0; i < 3; ++i)
@@ -1742,13 +1760,17 @@ void Engine::fused_sgd(uintptr_t mom, uintptr_t grad, double lr,
     hip_fused_sgd(reinterpret_cast<float*>(mom),
                   reinterpret_cast<const float*>(grad), static_cast<float>(lr),
                   static_cast<float>(momentum), n_, values_, d[0], d[1], d[2],
-                  cfg_.delta_bf16, reinterpret_cast<hipStream_t>(stream));
+                  cfg_.delta_bf16, reinterpret_cast<hipStream_t>(stream),
+                  clip);
   } else {
+    if (clip && clip->skip) return;  // nothing staged: no sender to wake
+    const float coef = clip ? clip->coef : 1.0f;
     float* m = reinterpret_cast<float*>(mom);
     const float* g = reinterpret_cast<const float*>(grad);
     cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
       for (int64_t i = lo; i < hi; ++i) {
-        float mm = static_cast<float>(momentum) * m[i] + g[i];
+        float gi = clip ? mul_uncontracted_f32(g[i], coef) : g[i];
+        float mm = static_cast<float>(momentum) * m[i] + gi;
         m[i] = mm;
         float u = static_cast<float>(-lr) * mm;
         if (u == 0.0f) continue;
@@ -1763,7 +1785,7 @@ void Engine::fused_sgd(uintptr_t mom, uintptr_t grad, double lr,
 
 void Engine::fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                             uintptr_t shadow_bf16, double lr, double momentum,
-                            uintptr_t stream) {
+                            uintptr_t stream, uintptr_t clip_state) {
   if (!gpu())
     throw std::runtime_error("fused_sgd_bf16 is a GPU-only path");
   std::shared_lock<std::shared_mutex> ug(user_m_);
@@ -1775,14 +1797,17 @@ void Engine::fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                      reinterpret_cast<uint16_t*>(shadow_bf16),
                      static_cast<float>(lr), static_cast<float>(momentum), n_,
                      values_, d[0], d[1], d[2], cfg_.delta_bf16,
-                     reinterpret_cast<hipStream_t>(stream));
+                     reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const ClipState*>(clip_state));
   notify_all_dirty();
 }
 
 void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                          bool grad_bf16, uintptr_t shadow, double lr,
                          double beta1, double beta2, double eps, double wd,
-                         int64_t step, uintptr_t stream) {
+                         int64_t step, uintptr_t stream,
+                         uintptr_t clip_state) {
+  const ClipState* clip = reinterpret_cast<const ClipState*>(clip_state);
   if (step < 1) throw std::runtime_error("fused_adamw: step must be >= 1");
   if (grad_bf16 && !gpu())
     throw std::runtime_error("bf16 grads are a GPU-only path");
@@ -1803,8 +1828,10 @@ void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                     static_cast<float>(lr), b1, b2, static_cast<float>(eps),
                     static_cast<float>(wd), inv_bc1, inv_bc2, n_, values_,
                     d[0], d[1], d[2], cfg_.delta_bf16,
-                    reinterpret_cast<hipStream_t>(stream));
+                    reinterpret_cast<hipStream_t>(stream), clip);
   } else {
+    if (clip && clip->skip) return;  // nothing staged: no sender to wake
+    const float coef = clip ? clip->coef : 1.0f;
     float* m = reinterpret_cast<float*>(mom);
     float* v = reinterpret_cast<float*>(vel);
     const float* g = reinterpret_cast<const float*>(grad);
@@ -1812,7 +1839,7 @@ void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
     const float wdf = static_cast<float>(wd);
     cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
       for (int64_t i = lo; i < hi; ++i) {
-        float gi = g[i];
+        float gi = clip ? mul_uncontracted_f32(g[i], coef) : g[i];
         float mi = b1 * m[i] + (1.f - b1) * gi;
         m[i] = mi;
         float vi = b2 * v[i] + (1.f - b2) * gi * gi;

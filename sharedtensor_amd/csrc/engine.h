@@ -78,14 +78,28 @@ class Engine {
   void start();  // join the tree (blocking, incl. snapshot); throws on error
   void add_from(uintptr_t src, int64_t n, uintptr_t stream);
   void copy_to(uintptr_t dst, int64_t n, uintptr_t stream);
+  // clip_state (all three steps): 0, or the ClipState that grad_clip_coef
+  // wrote, in the engine's memory space.  With skip set the step touches
+  // nothing and wakes no sender on the CPU; on the GPU the host cannot know
+  // and wakes them as usual.  Otherwise fl32(g * coef) replaces g.
   void fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double momentum,
-                 uintptr_t stream);
+                 uintptr_t stream, uintptr_t clip_state = 0);
   void fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16, uintptr_t shadow_bf16,
-                      double lr, double momentum, uintptr_t stream);
+                      double lr, double momentum, uintptr_t stream,
+                      uintptr_t clip_state = 0);
   // shadow==0: fp32 grads, no shadow refresh (grad_bf16 must be false)
   void fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad, bool grad_bf16,
                    uintptr_t shadow, double lr, double beta1, double beta2,
-                   double eps, double wd, int64_t step, uintptr_t stream);
+                   double eps, double wd, int64_t step, uintptr_t stream,
+                   uintptr_t clip_state = 0);
+  // Global gradient norm and clip coefficient of grad[0, n) into *state (32
+  // bytes, common.h ClipState; zeroed once by the caller).  GPU engines:
+  // two launches on `stream`, scratch = GRAD_CLIP_MAX_BLOCKS device doubles.
+  // CPU engines: fp32 gradients only, scratch unused.  Throws
+  // std::invalid_argument unless max_norm is finite and > 0.
+  void grad_clip_coef(uintptr_t grad, bool grad_bf16, int64_t n,
+                      double max_norm, uintptr_t scratch, uintptr_t state,
+                      uintptr_t stream);
   void notify_dirty();  // wake senders after out-of-band delta writes
   void close();
 

@@ -78,7 +78,8 @@ void hip_add_delta_scatter(const void* src_delta, bool delta_bf16, int64_t n,
 // u = -lr*m; {values, link deltas} += u.  One pass over HBM instead of four.
 void hip_fused_sgd(float* mom, const float* grad, float lr, float momentum,
                    int64_t n, float* values, void* d1, void* d2, void* d3,
-                   bool delta_bf16, hipStream_t s);
+                   bool delta_bf16, hipStream_t s,
+                   const ClipState* clip = nullptr);
 
 // Mixed-precision variant: bf16 grads in, fp32 master (values) updated,
 // bf16 shadow params refreshed (folding concurrent gossip via the
@@ -86,7 +87,7 @@ void hip_fused_sgd(float* mom, const float* grad, float lr, float momentum,
 void hip_fused_sgd_bf16(float* mom, const uint16_t* grad, uint16_t* shadow,
                         float lr, float momentum, int64_t n, float* values,
                         void* d1, void* d2, void* d3, bool delta_bf16,
-                        hipStream_t s);
+                        hipStream_t s, const ClipState* clip = nullptr);
 
 // Fused AdamW feeding the shared tensor (torch.optim.AdamW semantics:
 // decoupled weight decay on the pre-update weight): m/v fp32 state, grads
@@ -96,7 +97,28 @@ void hip_fused_adamw(float* mom, float* vel, const void* grad, bool grad_bf16,
                      uint16_t* shadow, float lr, float beta1, float beta2,
                      float eps, float wd, float inv_bc1, float inv_bc2,
                      int64_t n, float* values, void* d1, void* d2, void* d3,
-                     bool delta_bf16, hipStream_t s);
+                     bool delta_bf16, hipStream_t s,
+                     const ClipState* clip = nullptr);
+
+// Global-norm gradient clipping (grad_clip_kernels.hip).  One read-only pass
+// over grad (fp32, or bf16 with grad_bf16; aligned to its element size, any
+// n >= 1) sums g*g in fp64 into one partial per block, a one-block kernel
+// sums the partials in index order and writes *state (common.h ClipState):
+// no atomics, so the state repeats bit for bit.  `scratch` holds
+// GRAD_CLIP_MAX_BLOCKS doubles and needs no zeroing; `state` must be zeroed
+// once before its first use (skipped_total is only ever incremented).  Both
+// launches go to `s` with nothing in between.  Throws std::invalid_argument
+// before any launch unless max_norm is finite and > 0.
+//
+// The fused optimizers above take that state as `clip` (device memory, may
+// be null).  Null: the kernels and their results are what they are without
+// clipping.  skip set: every thread returns before any load or store of
+// mom, vel, values, shadow or the residuals.  Otherwise fl32(g * coef),
+// rounded once and never contracted into the following FMA, stands wherever
+// g stood; bf16 gradients are widened first and never rounded back.
+void hip_grad_clip_coef(const void* grad, bool grad_bf16, int64_t n,
+                        double max_norm, double* scratch, ClipState* state,
+                        hipStream_t s);
 
 // Fused bf16 LayerNorm for the training path (ln_kernels.hip): fwd saves
 // fp32 mean/rstd; bwd = dx pass + register-accumulated dgamma/dbeta pass.

@@ -74,6 +74,14 @@ __device__ __forceinline__ float add_uncontracted(float a, float b) {
   return a + b;
 }
 
+// g * coef rounded to fp32 on its own (gradient clipping): the optimizers
+// use the rounded product wherever they used g, so a clipped step equals an
+// unclipped step on gradients scaled beforehand, bit for bit.
+__device__ __forceinline__ float mul_uncontracted(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // Residual-delta storage policies --------------------------------------
 
 struct DeltaF32 {
@@ -491,15 +499,32 @@ __global__ void k_snapshot_capture(const float* __restrict__ values,
   }
 }
 
-template <typename DP>
+// CLIP (all three fused optimizers): `clip` is the state grad_clip_coef
+// wrote.  skip set: every thread returns before it touches any buffer.
+// Otherwise the gradient is fl32(g * coef).  Without CLIP the pointer is
+// unused and the kernel is what it was before clipping existed.
+//
+// The moment updates spell out which product is fused into the sum and
+// which is rounded on its own.  Left to the compiler, the choice differed
+// between instantiations (a packed multiply instead of the FMA once g was
+// itself a product), and a clipped step was no longer the unclipped step on
+// scaled gradients.  The forms below are the ones the compiler had picked
+// for the kernels without clipping, so those compute what they always did.
+template <typename DP, bool CLIP>
 __global__ void k_fused_sgd(float* __restrict__ mom,
                             const float* __restrict__ grad, float lr,
                             float momentum, int64_t n, float* values,
                             typename DP::T* d1, typename DP::T* d2,
-                            typename DP::T* d3) {
+                            typename DP::T* d3, const ClipState* clip) {
+  float coef = 1.0f;
+  if (CLIP) {
+    if (clip->skip) return;
+    coef = clip->coef;
+  }
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += gstride) {
-    float m = momentum * mom[i] + grad[i];
+    float g = CLIP ? mul_uncontracted(grad[i], coef) : grad[i];
+    float m = fmaf(momentum, mom[i], g);
     mom[i] = m;
     float u = -lr * m;
     if (values) atomicAdd(values + i, u);
@@ -513,17 +538,24 @@ __global__ void k_fused_sgd(float* __restrict__ mom,
 // bf16 shadow parameters out — one HBM pass covering what autocast training
 // otherwise spends three cast/copy kernel families on.  The atomicAdd's
 // return value folds any concurrently-applied gossip into the shadow.
-template <typename DP>
+template <typename DP, bool CLIP>
 __global__ void k_fused_sgd_bf16(float* __restrict__ mom,
                                  const uint16_t* __restrict__ grad,
                                  uint16_t* __restrict__ shadow, float lr,
                                  float momentum, int64_t n,
                                  float* __restrict__ values,
                                  typename DP::T* d1, typename DP::T* d2,
-                                 typename DP::T* d3) {
+                                 typename DP::T* d3, const ClipState* clip) {
+  float coef = 1.0f;
+  if (CLIP) {
+    if (clip->skip) return;
+    coef = clip->coef;
+  }
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += gstride) {
-    float m = momentum * mom[i] + bf16_to_f32(grad[i]);
+    float g = bf16_to_f32(grad[i]);
+    if (CLIP) g = mul_uncontracted(g, coef);
+    float m = fmaf(momentum, mom[i], g);
     mom[i] = m;
     float u = -lr * m;
     float old = atomicAdd(values + i, u);
@@ -701,21 +733,29 @@ __device__ __forceinline__ float gval(const uint16_t* g, int64_t i) {
   return bf16_to_f32(g[i]);
 }
 
-template <typename DP, typename GT>
+template <typename DP, typename GT, bool CLIP>
 __global__ void k_fused_adamw(float* __restrict__ mom, float* __restrict__ vel,
                               const GT* __restrict__ grad,
                               uint16_t* __restrict__ shadow, float lr,
                               float beta1, float beta2, float eps, float wd,
                               float inv_bc1, float inv_bc2, int64_t n,
                               float* __restrict__ values, typename DP::T* d1,
-                              typename DP::T* d2, typename DP::T* d3) {
+                              typename DP::T* d2, typename DP::T* d3,
+                              const ClipState* clip) {
+  float coef = 1.0f;
+  if (CLIP) {
+    if (clip->skip) return;
+    coef = clip->coef;
+  }
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gstride) {
     float g = gval(grad, i);
-    float m = beta1 * mom[i] + (1.f - beta1) * g;
+    if (CLIP) g = mul_uncontracted(g, coef);
+    float m = fmaf(1.f - beta1, g, mul_uncontracted(beta1, mom[i]));
     mom[i] = m;
-    float v = beta2 * vel[i] + (1.f - beta2) * g * g;
+    float v = fmaf(g, mul_uncontracted(1.f - beta2, g),
+                   mul_uncontracted(beta2, vel[i]));
     vel[i] = v;
     float w = __hip_atomic_load(values + i, __ATOMIC_RELAXED,
                                 __HIP_MEMORY_SCOPE_AGENT);
@@ -732,56 +772,69 @@ void hip_fused_adamw(float* mom, float* vel, const void* grad, bool grad_bf16,
                      uint16_t* shadow, float lr, float beta1, float beta2,
                      float eps, float wd, float inv_bc1, float inv_bc2,
                      int64_t n, float* values, void* d1, void* d2, void* d3,
-                     bool delta_bf16, hipStream_t s) {
-  auto launch = [&](auto dp_tag, auto g_ptr) {
+                     bool delta_bf16, hipStream_t s, const ClipState* clip) {
+  auto launch = [&](auto dp_tag, auto g_ptr, auto clip_tag) {
     using DP = decltype(dp_tag);
-    hipLaunchKernelGGL((k_fused_adamw<DP, std::remove_pointer_t<decltype(g_ptr)>>),
+    using GT = std::remove_pointer_t<decltype(g_ptr)>;
+    hipLaunchKernelGGL((k_fused_adamw<DP, GT, decltype(clip_tag)::value>),
                        dim3(grid_for(n)), dim3(BLOCK), 0, s, mom, vel, g_ptr,
                        shadow, lr, beta1, beta2, eps, wd, inv_bc1, inv_bc2, n,
                        values, static_cast<typename DP::T*>(d1),
                        static_cast<typename DP::T*>(d2),
-                       static_cast<typename DP::T*>(d3));
+                       static_cast<typename DP::T*>(d3), clip);
   };
-  if (delta_bf16) {
-    if (grad_bf16) launch(DeltaBF16{}, static_cast<const uint16_t*>(grad));
-    else launch(DeltaBF16{}, static_cast<const float*>(grad));
-  } else {
-    if (grad_bf16) launch(DeltaF32{}, static_cast<const uint16_t*>(grad));
-    else launch(DeltaF32{}, static_cast<const float*>(grad));
-  }
+  auto by_grad = [&](auto dp_tag, auto clip_tag) {
+    if (grad_bf16) launch(dp_tag, static_cast<const uint16_t*>(grad), clip_tag);
+    else launch(dp_tag, static_cast<const float*>(grad), clip_tag);
+  };
+  auto by_delta = [&](auto clip_tag) {
+    if (delta_bf16) by_grad(DeltaBF16{}, clip_tag);
+    else by_grad(DeltaF32{}, clip_tag);
+  };
+  if (clip) by_delta(std::true_type{});
+  else by_delta(std::false_type{});
   HIP_CHECK(hipGetLastError());
 }
 
 void hip_fused_sgd(float* mom, const float* grad, float lr, float momentum,
                    int64_t n, float* values, void* d1, void* d2, void* d3,
-                   bool delta_bf16, hipStream_t s) {
-  if (delta_bf16)
-    hipLaunchKernelGGL((k_fused_sgd<DeltaBF16>), dim3(grid_for(n)), dim3(BLOCK),
-                       0, s, mom, grad, lr, momentum, n, values,
-                       static_cast<uint16_t*>(d1), static_cast<uint16_t*>(d2),
-                       static_cast<uint16_t*>(d3));
-  else
-    hipLaunchKernelGGL((k_fused_sgd<DeltaF32>), dim3(grid_for(n)), dim3(BLOCK),
-                       0, s, mom, grad, lr, momentum, n, values,
-                       static_cast<float*>(d1), static_cast<float*>(d2),
-                       static_cast<float*>(d3));
+                   bool delta_bf16, hipStream_t s, const ClipState* clip) {
+  auto launch = [&](auto dp_tag, auto clip_tag) {
+    using DP = decltype(dp_tag);
+    hipLaunchKernelGGL((k_fused_sgd<DP, decltype(clip_tag)::value>),
+                       dim3(grid_for(n)), dim3(BLOCK), 0, s, mom, grad, lr,
+                       momentum, n, values, static_cast<typename DP::T*>(d1),
+                       static_cast<typename DP::T*>(d2),
+                       static_cast<typename DP::T*>(d3), clip);
+  };
+  auto by_delta = [&](auto clip_tag) {
+    if (delta_bf16) launch(DeltaBF16{}, clip_tag);
+    else launch(DeltaF32{}, clip_tag);
+  };
+  if (clip) by_delta(std::true_type{});
+  else by_delta(std::false_type{});
   HIP_CHECK(hipGetLastError());
 }
 
 void hip_fused_sgd_bf16(float* mom, const uint16_t* grad, uint16_t* shadow,
                         float lr, float momentum, int64_t n, float* values,
                         void* d1, void* d2, void* d3, bool delta_bf16,
-                        hipStream_t s) {
-  if (delta_bf16)
-    hipLaunchKernelGGL((k_fused_sgd_bf16<DeltaBF16>), dim3(grid_for(n)),
-                       dim3(BLOCK), 0, s, mom, grad, shadow, lr, momentum, n,
-                       values, static_cast<uint16_t*>(d1),
-                       static_cast<uint16_t*>(d2), static_cast<uint16_t*>(d3));
-  else
-    hipLaunchKernelGGL((k_fused_sgd_bf16<DeltaF32>), dim3(grid_for(n)),
-                       dim3(BLOCK), 0, s, mom, grad, shadow, lr, momentum, n,
-                       values, static_cast<float*>(d1), static_cast<float*>(d2),
-                       static_cast<float*>(d3));
+                        hipStream_t s, const ClipState* clip) {
+  auto launch = [&](auto dp_tag, auto clip_tag) {
+    using DP = decltype(dp_tag);
+    hipLaunchKernelGGL((k_fused_sgd_bf16<DP, decltype(clip_tag)::value>),
+                       dim3(grid_for(n)), dim3(BLOCK), 0, s, mom, grad, shadow,
+                       lr, momentum, n, values,
+                       static_cast<typename DP::T*>(d1),
+                       static_cast<typename DP::T*>(d2),
+                       static_cast<typename DP::T*>(d3), clip);
+  };
+  auto by_delta = [&](auto clip_tag) {
+    if (delta_bf16) launch(DeltaBF16{}, clip_tag);
+    else launch(DeltaF32{}, clip_tag);
+  };
+  if (clip) by_delta(std::true_type{});
+  else by_delta(std::false_type{});
   HIP_CHECK(hipGetLastError());
 }
 

@@ -82,6 +82,8 @@ class _SharedBase:
         self.n = int(sum(sizes))
         self._cfg = cfg
         self._closed = False
+        self._clip_state = None      # allocated by the first grad_clip_coef
+        self._clip_scratch = None
 
         msg = _core.msg_bytes(cfg)
         self.values = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -163,21 +165,83 @@ class _SharedBase:
             raise TypeError("expected a contiguous float32 tensor")
         self._eng.copy_to(flat.data_ptr(), flat.numel(), self._stream())
 
+    def grad_clip_coef(self, grad: torch.Tensor,
+                       max_norm: float) -> torch.Tensor:
+        """Global L2 norm of the flat gradient and torch's clip coefficient
+        min(1, max_norm / (norm + 1e-6)), computed on the engine's device
+        and stream with no host sync (HIP kernels k_grad_sumsq and
+        k_grad_clip_finalize: fp64, no atomics, bitwise reproducible).
+
+        Returns the 32-byte clip state as 8 int32 words on the engine's
+        device; hand it to a fused step as `clip_state`.  The same tensor is
+        written again by every call.  Layout: f64 sumsq | f32 norm | f32
+        coef | u32 skip | u32 skipped_total | 8 bytes padding.  skip is 1
+        when some gradient is inf or NaN (coef is then 0 and a fused step
+        given this state changes nothing); skipped_total counts such calls.
+        `decode_clip_state` turns it into python numbers (that one syncs)."""
+        max_norm = float(max_norm)
+        if not (max_norm > 0.0 and max_norm != float("inf")):
+            raise ValueError("max_norm must be finite and > 0")
+        if grad.numel() != self.n or not grad.is_contiguous():
+            raise ValueError("grad must be the contiguous flat gradient")
+        if grad.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("grad must be float32 or bfloat16")
+        if grad.device.type != self.device.type:
+            raise ValueError("grad must live on the engine's device")
+        if self._clip_state is None:
+            self._clip_state = torch.zeros(8, dtype=torch.int32,
+                                           device=self.device)
+            self._clip_scratch = torch.empty(
+                _core.GRAD_CLIP_MAX_BLOCKS if self._gpu else 1,
+                dtype=torch.float64, device=self.device)
+        self._eng.grad_clip_coef(grad.data_ptr(),
+                                 grad.dtype == torch.bfloat16, self.n,
+                                 max_norm, self._clip_scratch.data_ptr(),
+                                 self._clip_state.data_ptr(), self._stream())
+        return self._clip_state
+
+    @staticmethod
+    def decode_clip_state(state: torch.Tensor) -> dict:
+        """The clip state as python numbers.  Copies to the host, which
+        waits for the work queued before it."""
+        w = state.detach().cpu()
+        return {"sumsq": float(w[0:2].view(torch.float64)[0]),
+                "grad_norm": float(w[2:3].view(torch.float32)[0]),
+                "clip_coef": float(w[3:4].view(torch.float32)[0]),
+                "skipped": bool(int(w[4]) & 0xFFFFFFFF),
+                "skipped_steps": int(w[5]) & 0xFFFFFFFF}
+
+    def _clip_ptr(self, clip_state: Optional[torch.Tensor]) -> int:
+        if clip_state is None:
+            return 0
+        if (clip_state.dtype != torch.int32 or clip_state.numel() != 8
+                or not clip_state.is_contiguous()
+                or clip_state.device.type != self.device.type):
+            raise TypeError("clip_state must be the 8-word int32 tensor that "
+                            "grad_clip_coef returned")
+        return clip_state.data_ptr()
+
     def fused_sgd_step(self, momentum_buf: torch.Tensor, grad: torch.Tensor,
-                       lr: float, momentum: float = 0.9):
+                       lr: float, momentum: float = 0.9,
+                       clip_state: Optional[torch.Tensor] = None):
         """m = mu*m + g; u = -lr*m; {replica, link deltas} += u — one fused
-        HBM pass (HIP kernel k_fused_sgd) instead of optimizer + addFromTensor."""
+        HBM pass (HIP kernel k_fused_sgd) instead of optimizer + addFromTensor.
+        With `clip_state` (see grad_clip_coef) g is fl32(g * coef), or the
+        step changes nothing when the state says skip."""
         if momentum_buf.numel() != self.n or grad.numel() != self.n:
             raise ValueError("size mismatch")
         self._eng.fused_sgd(momentum_buf.data_ptr(), grad.data_ptr(),
-                            float(lr), float(momentum), self._stream())
+                            float(lr), float(momentum), self._stream(),
+                            self._clip_ptr(clip_state))
 
     def fused_sgd_bf16_step(self, momentum_buf: torch.Tensor,
                             grad_bf16: torch.Tensor, shadow_bf16: torch.Tensor,
-                            lr: float, momentum: float = 0.9):
+                            lr: float, momentum: float = 0.9,
+                            clip_state: Optional[torch.Tensor] = None):
         """Mixed-precision fused step: bf16 grads in, fp32 master updated,
         bf16 shadow params refreshed, link deltas staged — one HBM pass
-        (HIP kernel k_fused_sgd_bf16)."""
+        (HIP kernel k_fused_sgd_bf16).  `clip_state`: as fused_sgd_step; the
+        scaled gradient stays fp32."""
         if grad_bf16.dtype != torch.bfloat16 or shadow_bf16.dtype != torch.bfloat16:
             raise TypeError("grad/shadow must be bfloat16")
         if not (momentum_buf.numel() == grad_bf16.numel()
@@ -185,16 +249,19 @@ class _SharedBase:
             raise ValueError("size mismatch")
         self._eng.fused_sgd_bf16(momentum_buf.data_ptr(), grad_bf16.data_ptr(),
                                  shadow_bf16.data_ptr(), float(lr),
-                                 float(momentum), self._stream())
+                                 float(momentum), self._stream(),
+                                 self._clip_ptr(clip_state))
 
     def fused_adamw_step(self, mom: torch.Tensor, vel: torch.Tensor,
                          grad: torch.Tensor, step: int, lr: float,
                          betas=(0.9, 0.999), eps: float = 1e-8,
-                         weight_decay: float = 0.0):
+                         weight_decay: float = 0.0,
+                         clip_state: Optional[torch.Tensor] = None):
         """torch.optim.AdamW-semantics update feeding the shared tensor:
         fp32 m/v, decoupled weight decay on the pre-update master weight,
         update applied to the replica AND staged into every link delta in
-        one HBM pass (HIP kernel k_fused_adamw)."""
+        one HBM pass (HIP kernel k_fused_adamw).  `clip_state`: as
+        fused_sgd_step; a skipped step leaves m, v and the weights alone."""
         if not (mom.numel() == vel.numel() == grad.numel() == self.n):
             raise ValueError("size mismatch")
         if grad.dtype != torch.float32:
@@ -203,16 +270,18 @@ class _SharedBase:
         self._eng.fused_adamw(mom.data_ptr(), vel.data_ptr(), grad.data_ptr(),
                               False, 0, float(lr), float(betas[0]),
                               float(betas[1]), float(eps),
-                              float(weight_decay), int(step), self._stream())
+                              float(weight_decay), int(step), self._stream(),
+                              self._clip_ptr(clip_state))
 
     def fused_adamw_bf16_step(self, mom: torch.Tensor, vel: torch.Tensor,
                               grad_bf16: torch.Tensor,
                               shadow_bf16: torch.Tensor, step: int, lr: float,
                               betas=(0.9, 0.999), eps: float = 1e-8,
-                              weight_decay: float = 0.0):
+                              weight_decay: float = 0.0,
+                              clip_state: Optional[torch.Tensor] = None):
         """Mixed-precision fused AdamW: bf16 grads in, fp32 master updated,
         bf16 shadow params refreshed (folding concurrent gossip), link
-        deltas staged — one HBM pass."""
+        deltas staged — one HBM pass.  `clip_state`: as fused_adamw_step."""
         if grad_bf16.dtype != torch.bfloat16 or shadow_bf16.dtype != torch.bfloat16:
             raise TypeError("grad/shadow must be bfloat16")
         if not (mom.numel() == vel.numel() == grad_bf16.numel()
@@ -222,7 +291,8 @@ class _SharedBase:
                               grad_bf16.data_ptr(), True,
                               shadow_bf16.data_ptr(), float(lr),
                               float(betas[0]), float(betas[1]), float(eps),
-                              float(weight_decay), int(step), self._stream())
+                              float(weight_decay), int(step), self._stream(),
+                              self._clip_ptr(clip_state))
 
     # -- observability -----------------------------------------------------
     def stats(self) -> dict:

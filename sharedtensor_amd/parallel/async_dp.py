@@ -13,9 +13,16 @@ This module wires a torch model into that scheme MI355X-style:
   * the optimizer update is ONE fused HIP kernel (k_fused_sgd) that computes
     momentum, applies -lr*m to the replica AND stages it into every link's
     residual delta in a single HBM pass.
+  * optional global-norm gradient clipping (max_grad_norm): one extra
+    read-only pass over the flat gradient leaves the clip coefficient in
+    device memory, the fused step reads it from there — no host sync, no
+    extra gradient write — and a step whose gradient holds an inf or NaN
+    is skipped on the device, so it never reaches the replica or the link
+    residuals.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -101,40 +108,88 @@ class FlatParamShared(_SharedBase):
         self.world = world
 
 
-class AsyncSGD:
+def _check_max_grad_norm(max_grad_norm: Optional[float]) -> Optional[float]:
+    if max_grad_norm is None:
+        return None
+    c = float(max_grad_norm)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError("max_grad_norm must be finite and > 0 (or None)")
+    return c
+
+
+class _ClipMixin:
+    """max_grad_norm handling shared by the two optimizers: this rank's own
+    global L2 norm (each rank takes its own step, so each clips its own
+    gradient), torch's clip_grad_norm_ coefficient, and a step that is
+    skipped on the device when the gradient holds an inf or NaN."""
+
+    def _clip_state(self) -> Optional[torch.Tensor]:
+        if self.max_grad_norm is None:
+            return None
+        return self.shared.grad_clip_coef(self.shared.grad_flat,
+                                          self.max_grad_norm)
+
+    def grad_stats(self) -> Optional[dict]:
+        """{"grad_norm", "clip_coef", "skipped", "skipped_steps"} of the
+        latest step (syncs), or None when clipping is off or no step ran."""
+        if self.max_grad_norm is None or self.shared._clip_state is None:
+            return None
+        d = self.shared.decode_clip_state(self.shared._clip_state)
+        del d["sumsq"]
+        return d
+
+
+class AsyncSGD(_ClipMixin):
     """SGD-momentum whose update feeds the shared tensor through the fused
-    kernel — the optimizer step IS the addFromTensor."""
+    kernel — the optimizer step IS the addFromTensor.
+
+    max_grad_norm: clip this rank's gradient to that global L2 norm inside
+    the fused step; a non-finite gradient skips the step (momentum, weights
+    and link residuals untouched)."""
 
     def __init__(self, shared: FlatParamShared, lr: float = 0.1,
-                 momentum: float = 0.9):
+                 momentum: float = 0.9,
+                 max_grad_norm: Optional[float] = None):
         self.shared = shared
         self.lr = lr
         self.momentum = momentum
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
 
     def step(self):
+        clip = self._clip_state()
         if self.shared.shadow is not None:
             self.shared.fused_sgd_bf16_step(self.shared.mom_flat,
                                             self.shared.grad_flat,
                                             self.shared.shadow, self.lr,
-                                            self.momentum)
+                                            self.momentum, clip_state=clip)
         else:
             self.shared.fused_sgd_step(self.shared.mom_flat,
                                        self.shared.grad_flat,
-                                       self.lr, self.momentum)
+                                       self.lr, self.momentum,
+                                       clip_state=clip)
 
     def zero_grad(self, set_to_none: bool = False):
         self.shared.grad_flat.zero_()
 
 
-class AsyncAdamW:
+class AsyncAdamW(_ClipMixin):
     """AdamW whose update feeds the shared tensor through the fused kernel
     (torch.optim.AdamW semantics: decoupled weight decay on the pre-update
-    master weight) — the optimizer step IS the addFromTensor."""
+    master weight) — the optimizer step IS the addFromTensor.
+
+    max_grad_norm: clip this rank's gradient to that global L2 norm inside
+    the fused step; a non-finite gradient skips the step (m, v, weights,
+    shadow and link residuals untouched).  Deviation from a host-side
+    skip: `step_count`, and with it the bias correction, still advances on
+    a skipped step, because the host cannot know about the skip without a
+    sync."""
 
     def __init__(self, shared: FlatParamShared, lr: float = 3e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.01):
+                 weight_decay: float = 0.01,
+                 max_grad_norm: Optional[float] = None):
         self.shared = shared
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
         self.lr = lr
         self.betas = betas
         self.eps = eps
@@ -146,21 +201,27 @@ class AsyncAdamW:
     def step(self):
         self.step_count += 1
         sh = self.shared
+        clip = self._clip_state()
         if sh.shadow is not None:
             sh.fused_adamw_bf16_step(sh.mom_flat, self.vel_flat, sh.grad_flat,
                                      sh.shadow, self.step_count, self.lr,
-                                     self.betas, self.eps, self.weight_decay)
+                                     self.betas, self.eps, self.weight_decay,
+                                     clip_state=clip)
         else:
             sh.fused_adamw_step(sh.mom_flat, self.vel_flat, sh.grad_flat,
                                 self.step_count, self.lr, self.betas,
-                                self.eps, self.weight_decay)
+                                self.eps, self.weight_decay, clip_state=clip)
 
     def zero_grad(self, set_to_none: bool = False):
         self.shared.grad_flat.zero_()
 
 
 class AsyncDPTrainer:
-    """One rank's training loop against the shared parameter tensor."""
+    """One rank's training loop against the shared parameter tensor.
+
+    max_grad_norm (default None: off) clips this rank's gradient to that
+    global L2 norm inside the fused optimizer step and skips a step whose
+    gradient is not finite; see AsyncSGD / AsyncAdamW and grad_stats()."""
 
     def __init__(self, model: torch.nn.Module, host: str = "127.0.0.1",
                  port_base: Optional[int] = None, rank: Optional[int] = None,
@@ -168,7 +229,9 @@ class AsyncDPTrainer:
                  momentum: float = 0.9, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
                  param_dtype: Optional[torch.dtype] = None,
                  optimizer: str = "sgd", betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, **engine_kw):
+                 eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None, **engine_kw):
+        max_grad_norm = _check_max_grad_norm(max_grad_norm)
         rank = int(os.environ.get("RANK", 0)) if rank is None else rank
         world = int(os.environ.get("WORLD_SIZE", 1)) if world is None else world
         if port_base is None:
@@ -180,9 +243,11 @@ class AsyncDPTrainer:
                                       param_dtype=param_dtype, **engine_kw)
         if optimizer == "adamw":
             self.opt = AsyncAdamW(self.shared, lr=lr, betas=betas, eps=eps,
-                                  weight_decay=weight_decay)
+                                  weight_decay=weight_decay,
+                                  max_grad_norm=max_grad_norm)
         elif optimizer == "sgd":
-            self.opt = AsyncSGD(self.shared, lr=lr, momentum=momentum)
+            self.opt = AsyncSGD(self.shared, lr=lr, momentum=momentum,
+                                max_grad_norm=max_grad_norm)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         self.amp_dtype = amp_dtype
@@ -201,6 +266,14 @@ class AsyncDPTrainer:
 
     def stats(self):
         return self.shared.stats()
+
+    def grad_stats(self) -> Optional[dict]:
+        """Norm and clipping of the latest step: {"grad_norm": fp32 global
+        L2 norm before clipping (inf/nan on a skipped step), "clip_coef":
+        the factor applied (0 on a skipped step), "skipped": whether the
+        latest step was skipped, "skipped_steps": how many were so far}.
+        Waits for the device.  None when max_grad_norm is None."""
+        return self.opt.grad_stats()
 
     def close(self):
         self.shared.close()
