@@ -26,6 +26,7 @@ SOURCES = [
     "rccl_transport.cpp",
     "hip_kernels.hip",
     "grad_clip_kernels.hip",
+    "optim_group_kernels.hip",
     "ln_kernels.hip",
     "add_ln_kernels.hip",
     "add_rms_kernels.hip",
@@ -37,7 +38,8 @@ SOURCES = [
     "bindings.cpp",
 ]
 
-HEADERS = ["common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "rccl_transport.h"]
+HEADERS = ["common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "optim_step.h",
+           "rccl_transport.h"]
 
 
 def pybind11_include():

@@ -22,7 +22,7 @@ sys.path.insert(0, __file__.rsplit("/", 2)[0])
 def rank_main(args):
     import torch
     from sharedtensor_amd.models.gpt2 import GPT2, GPT2Config
-    from sharedtensor_amd.parallel.async_dp import AsyncDPTrainer
+    from sharedtensor_amd.parallel import AsyncDPTrainer, no_decay_groups
 
     rank = int(os.environ["RANK"])
     world = int(os.environ["WORLD_SIZE"])
@@ -35,7 +35,9 @@ def rank_main(args):
     model = GPT2(cfg).to(dev)
     trainer = AsyncDPTrainer(
         model, port_base=args.port, rank=rank, world=world,
-        lr=args.lr, optimizer=args.opt,
+        lr=args.lr, optimizer=args.opt, weight_decay=args.weight_decay,
+        param_groups=(no_decay_groups(model, args.weight_decay)
+                      if args.no_decay_groups else None),
         amp_dtype=torch.bfloat16 if dev.type == "cuda" else None,
         param_dtype=torch.bfloat16 if dev.type == "cuda" else torch.float32,
         codec=args.codec, sync_interval_s=0.05, snapshot_join=True,
@@ -72,7 +74,15 @@ def main():
                     help="clip each rank's gradient to this global L2 norm "
                          "inside the fused optimizer step; a step with an "
                          "inf/NaN gradient is skipped (default: off)")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="AdamW weight decay (the fused SGD step has none)")
+    ap.add_argument("--no-decay-groups", action="store_true",
+                    help="with --opt adamw: biases and LayerNorm gains "
+                         "(ndim < 2) are not decayed, through parameter "
+                         "groups inside the same fused step")
     args = ap.parse_args()
+    if args.opt == "sgd" and args.weight_decay:
+        ap.error("--weight-decay needs --opt adamw")
     if "RANK" in os.environ:
         rank_main(args)
         return

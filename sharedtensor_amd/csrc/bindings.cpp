@@ -127,9 +127,20 @@ void py_gpu_add_scatter(uintptr_t src, int64_t n, double alpha,
 // dsts[0] = fp32 values (or 0); dsts[1..3] = delta-typed
 void py_gpu_fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double mu,
                       int64_t n, std::vector<uintptr_t> dsts, uintptr_t stream,
-                      bool delta_bf16, uintptr_t clip_state) {
+                      bool delta_bf16, uintptr_t clip_state, uintptr_t groups) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
+  if (groups) {
+    hip_fused_sgd_grouped(
+        reinterpret_cast<float*>(mom), reinterpret_cast<const float*>(grad),
+        static_cast<float>(lr), static_cast<float>(mu), n,
+        reinterpret_cast<float*>(d[0]), reinterpret_cast<void*>(d[1]),
+        reinterpret_cast<void*>(d[2]), reinterpret_cast<void*>(d[3]),
+        delta_bf16, reinterpret_cast<hipStream_t>(stream),
+        reinterpret_cast<const ClipState*>(clip_state),
+        reinterpret_cast<const void*>(groups));
+    return;
+  }
   hip_fused_sgd(reinterpret_cast<float*>(mom),
                 reinterpret_cast<const float*>(grad), static_cast<float>(lr),
                 static_cast<float>(mu), n, reinterpret_cast<float*>(d[0]),
@@ -145,11 +156,24 @@ void py_gpu_fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                            uintptr_t shadow_bf16, double lr, double mu,
                            int64_t n, std::vector<uintptr_t> dsts,
                            uintptr_t stream, bool delta_bf16,
-                           uintptr_t clip_state) {
+                           uintptr_t clip_state, uintptr_t groups) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
   if (!d[0] || !shadow_bf16)
     throw std::runtime_error("gpu_fused_sgd_bf16: values and shadow required");
+  if (groups) {
+    hip_fused_sgd_bf16_grouped(
+        reinterpret_cast<float*>(mom),
+        reinterpret_cast<const uint16_t*>(grad_bf16),
+        reinterpret_cast<uint16_t*>(shadow_bf16), static_cast<float>(lr),
+        static_cast<float>(mu), n, reinterpret_cast<float*>(d[0]),
+        reinterpret_cast<void*>(d[1]), reinterpret_cast<void*>(d[2]),
+        reinterpret_cast<void*>(d[3]), delta_bf16,
+        reinterpret_cast<hipStream_t>(stream),
+        reinterpret_cast<const ClipState*>(clip_state),
+        reinterpret_cast<const void*>(groups));
+    return;
+  }
   hip_fused_sgd_bf16(reinterpret_cast<float*>(mom),
                      reinterpret_cast<const uint16_t*>(grad_bf16),
                      reinterpret_cast<uint16_t*>(shadow_bf16),
@@ -170,10 +194,26 @@ void py_gpu_fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                         double beta1, double beta2, double eps, double wd,
                         double inv_bc1, double inv_bc2, int64_t n,
                         std::vector<uintptr_t> dsts, uintptr_t stream,
-                        bool delta_bf16, uintptr_t clip_state) {
+                        bool delta_bf16, uintptr_t clip_state,
+                        uintptr_t groups) {
   uintptr_t d[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < dsts.size() && i < 4; ++i) d[i] = dsts[i];
   if (!d[0]) throw std::runtime_error("gpu_fused_adamw: values required");
+  if (groups) {  // wd is unused: the table holds each group's decay
+    hip_fused_adamw_grouped(
+        reinterpret_cast<float*>(mom), reinterpret_cast<float*>(vel),
+        reinterpret_cast<const void*>(grad), grad_bf16,
+        reinterpret_cast<uint16_t*>(shadow_bf16), static_cast<float>(lr),
+        static_cast<float>(beta1), static_cast<float>(beta2),
+        static_cast<float>(eps), static_cast<float>(inv_bc1),
+        static_cast<float>(inv_bc2), n, reinterpret_cast<float*>(d[0]),
+        reinterpret_cast<void*>(d[1]), reinterpret_cast<void*>(d[2]),
+        reinterpret_cast<void*>(d[3]), delta_bf16,
+        reinterpret_cast<hipStream_t>(stream),
+        reinterpret_cast<const ClipState*>(clip_state),
+        reinterpret_cast<const void*>(groups));
+    return;
+  }
   hip_fused_adamw(reinterpret_cast<float*>(mom), reinterpret_cast<float*>(vel),
                   reinterpret_cast<const void*>(grad), grad_bf16,
                   reinterpret_cast<uint16_t*>(shadow_bf16),
@@ -267,17 +307,17 @@ PYBIND11_MODULE(_core, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("fused_sgd", &Engine::fused_sgd, py::arg("mom"), py::arg("grad"),
            py::arg("lr"), py::arg("momentum"), py::arg("stream"),
-           py::arg("clip_state") = 0,
+           py::arg("clip_state") = 0, py::arg("groups") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("fused_sgd_bf16", &Engine::fused_sgd_bf16, py::arg("mom"),
            py::arg("grad"), py::arg("shadow"), py::arg("lr"),
-           py::arg("momentum"), py::arg("stream"), py::arg("clip_state") = 0,
+           py::arg("momentum"), py::arg("stream"), py::arg("clip_state") = 0, py::arg("groups") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("fused_adamw", &Engine::fused_adamw, py::arg("mom"),
            py::arg("vel"), py::arg("grad"), py::arg("grad_bf16"),
            py::arg("shadow"), py::arg("lr"), py::arg("beta1"),
            py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("step"),
-           py::arg("stream"), py::arg("clip_state") = 0,
+           py::arg("stream"), py::arg("clip_state") = 0, py::arg("groups") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("grad_clip_coef", &Engine::grad_clip_coef, py::arg("grad"),
            py::arg("grad_bf16"), py::arg("n"), py::arg("max_norm"),
@@ -325,21 +365,28 @@ PYBIND11_MODULE(_core, m) {
   m.def("gpu_fused_sgd", &py_gpu_fused_sgd, py::arg("mom"), py::arg("grad"),
         py::arg("lr"), py::arg("mu"), py::arg("n"), py::arg("dsts"),
         py::arg("stream"), py::arg("delta_bf16") = false,
-        py::arg("clip_state") = 0);
+        py::arg("clip_state") = 0, py::arg("groups") = 0);
   m.def("gpu_fused_sgd_bf16", &py_gpu_fused_sgd_bf16, py::arg("mom"),
         py::arg("grad"), py::arg("shadow"), py::arg("lr"), py::arg("mu"),
         py::arg("n"), py::arg("dsts"), py::arg("stream"),
-        py::arg("delta_bf16") = false, py::arg("clip_state") = 0);
+        py::arg("delta_bf16") = false, py::arg("clip_state") = 0, py::arg("groups") = 0);
   m.def("gpu_fused_adamw", &py_gpu_fused_adamw, py::arg("mom"),
         py::arg("vel"), py::arg("grad"), py::arg("grad_bf16"),
         py::arg("shadow"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("wd"), py::arg("inv_bc1"), py::arg("inv_bc2"),
         py::arg("n"), py::arg("dsts"), py::arg("stream"),
-        py::arg("delta_bf16") = false, py::arg("clip_state") = 0);
+        py::arg("delta_bf16") = false, py::arg("clip_state") = 0, py::arg("groups") = 0);
   m.def("gpu_grad_clip_coef", &py_gpu_grad_clip_coef, py::arg("grad"),
         py::arg("grad_bf16"), py::arg("n"), py::arg("max_norm"),
         py::arg("scratch"), py::arg("state"), py::arg("stream"));
   m.attr("GRAD_CLIP_MAX_BLOCKS") = GRAD_CLIP_MAX_BLOCKS;
+  // Parameter-group table (common.h): validated, coalesced, as int32 words.
+  m.def("build_group_table", &build_group_table, py::arg("n"),
+        py::arg("seg_end"), py::arg("seg_group"), py::arg("lr_scale"),
+        py::arg("weight_decay"));
+  m.attr("GROUP_MAX_SEGMENTS") = GROUP_MAX_SEGMENTS;
+  m.attr("GROUP_TILE") = GROUP_TILE;
+  m.attr("GROUP_GRID_BLOCKS") = GROUP_GRID_BLOCKS;
   m.def("gpu_snapshot_capture", &py_gpu_snapshot_capture, py::arg("values"),
         py::arg("delta"), py::arg("out"), py::arg("n"), py::arg("stream"),
         py::arg("delta_bf16") = false);

@@ -115,6 +115,67 @@ static_assert(sizeof(ClipState) == 32, "clip state layout is public");
 // for this many blocks.
 constexpr int GRAD_CLIP_MAX_BLOCKS = 2048;
 
+// Parameter-group table read by the fused optimizer steps: the flat buffer
+// of n elements as S contiguous segments, each belonging to one of G groups
+// with its own learning-rate scale and weight decay.  Device memory for GPU
+// engines, host memory for CPU engines, 8-byte aligned.  The layout is
+// public (python holds it as int32 words; docs/ARCHITECTURE.md):
+//
+//   byte  0            int64   n              (== seg_end[S-1])
+//   byte  8            int32   S              1 <= S <= GROUP_MAX_SEGMENTS
+//   byte 12            int32   G              1 <= G
+//   byte 16            int64   seg_end[S]     exclusive ends, strictly ascending
+//   byte 16 + 8*S      int32   seg_group[S]   in [0, G)
+//   byte 16 + 12*S     float   lr_scale[G]    finite, >= 0
+//   byte 16 + 12*S+4*G float   weight_decay[G]  finite, >= 0
+//
+// Adjacent segments never share a group (build_group_table merges them).
+// A segment's effective rate is fl32(lr * lr_scale[g]): one fp32 multiply
+// rounded on its own, then used wherever the ungrouped step uses lr.
+constexpr int GROUP_MAX_SEGMENTS = 4096;  // Llama-3-8B has 291 tensors
+// The grouped kernels walk the buffer in tiles of GROUP_TILE contiguous
+// elements, one block per tile, at most GROUP_GRID_BLOCKS blocks (the
+// launch geometry of the ungrouped kernels); a tile that holds a segment
+// boundary stages at most GROUP_TILE segments in LDS.
+constexpr int GROUP_TILE = 256;
+constexpr int GROUP_GRID_BLOCKS = 32768;
+constexpr int GROUP_HEADER_WORDS = 4;
+
+inline int64_t group_table_words(int64_t S, int64_t G) {
+  return GROUP_HEADER_WORDS + 3 * S + 2 * G;
+}
+
+struct GroupTableView {
+  int64_t n;
+  int32_t S, G;
+  const int64_t* seg_end;
+  const int32_t* seg_group;
+  const float* lr_scale;
+  const float* weight_decay;
+};
+
+// Host-side view of a table in host memory (CPU engines, tests).
+inline GroupTableView group_table_view(const void* table) {
+  const char* b = static_cast<const char*>(table);
+  GroupTableView v;
+  std::memcpy(&v.n, b, 8);
+  std::memcpy(&v.S, b + 8, 4);
+  std::memcpy(&v.G, b + 12, 4);
+  v.seg_end = reinterpret_cast<const int64_t*>(b + 16);
+  v.seg_group = reinterpret_cast<const int32_t*>(b + 16 + 8 * int64_t(v.S));
+  v.lr_scale = reinterpret_cast<const float*>(b + 16 + 12 * int64_t(v.S));
+  v.weight_decay = v.lr_scale + v.G;
+  return v;
+}
+
+// Validates (std::invalid_argument otherwise), merges adjacent segments of
+// one group and returns the table as int32 words.  Defined in engine.cpp.
+std::vector<int32_t> build_group_table(int64_t n,
+                                       const std::vector<int64_t>& seg_end,
+                                       const std::vector<int64_t>& seg_group,
+                                       const std::vector<double>& lr_scale,
+                                       const std::vector<double>& weight_decay);
+
 constexpr uint32_t MAGIC = 0x53544132;  // "STA2"
 constexpr uint16_t PROTO_VERSION = 2;
 

@@ -7,6 +7,7 @@
 #include <sys/socket.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1732,6 +1733,89 @@ void Engine::copy_to(uintptr_t dst, int64_t n, uintptr_t stream) {
   }
 }
 
+std::vector<int32_t> build_group_table(
+    int64_t n, const std::vector<int64_t>& seg_end,
+    const std::vector<int64_t>& seg_group, const std::vector<double>& lr_scale,
+    const std::vector<double>& weight_decay) {
+  auto bad = [](const std::string& what) {
+    throw std::invalid_argument("group table: " + what);
+  };
+  const size_t G = lr_scale.size();
+  if (G < 1) bad("at least one group is needed");
+  if (weight_decay.size() != G)
+    bad("lr_scale and weight_decay differ in length");
+  if (seg_end.empty()) bad("at least one segment is needed");
+  if (seg_group.size() != seg_end.size())
+    bad("seg_end and seg_group differ in length");
+  for (size_t g = 0; g < G; ++g) {
+    const float l = static_cast<float>(lr_scale[g]);
+    const float w = static_cast<float>(weight_decay[g]);
+    if (!(std::isfinite(l) && l >= 0.f)) bad("lr_scale must be finite and >= 0");
+    if (!(std::isfinite(w) && w >= 0.f))
+      bad("weight_decay must be finite and >= 0");
+  }
+  std::vector<int64_t> ends;
+  std::vector<int32_t> grps;
+  int64_t prev = 0;
+  for (size_t s = 0; s < seg_end.size(); ++s) {
+    if (seg_end[s] <= prev) bad("segment ends must be strictly ascending");
+    if (seg_group[s] < 0 || seg_group[s] >= static_cast<int64_t>(G))
+      bad("group index out of range");
+    prev = seg_end[s];
+    if (!grps.empty() && grps.back() == seg_group[s]) {
+      ends.back() = prev;  // same group as its neighbour: one segment
+    } else {
+      ends.push_back(prev);
+      grps.push_back(static_cast<int32_t>(seg_group[s]));
+    }
+  }
+  if (prev != n) bad("segments must end at n");
+  const size_t S = ends.size();
+  if (S > static_cast<size_t>(GROUP_MAX_SEGMENTS))
+    bad("more than GROUP_MAX_SEGMENTS segments");
+  std::vector<int32_t> words(group_table_words(S, G));
+  char* b = reinterpret_cast<char*>(words.data());
+  const int32_t s32 = static_cast<int32_t>(S), g32 = static_cast<int32_t>(G);
+  std::memcpy(b, &n, 8);
+  std::memcpy(b + 8, &s32, 4);
+  std::memcpy(b + 12, &g32, 4);
+  std::memcpy(b + 16, ends.data(), 8 * S);
+  std::memcpy(b + 16 + 8 * S, grps.data(), 4 * S);
+  for (size_t g = 0; g < G; ++g) {
+    const float l = static_cast<float>(lr_scale[g]);
+    const float w = static_cast<float>(weight_decay[g]);
+    std::memcpy(b + 16 + 12 * S + 4 * g, &l, 4);
+    std::memcpy(b + 16 + 12 * S + 4 * G + 4 * g, &w, 4);
+  }
+  return words;
+}
+
+namespace {
+
+// A CPU engine's table lives in host memory, so its header can be checked
+// at every step.
+GroupTableView checked_group_view(const void* table, int64_t n) {
+  const GroupTableView tv = group_table_view(table);
+  if (tv.n != n || tv.S < 1 || tv.S > GROUP_MAX_SEGMENTS || tv.G < 1)
+    throw std::invalid_argument("group table does not describe this tensor");
+  return tv;
+}
+
+// f(a, b, group) for every piece [a, b) of [lo, hi) that lies in one segment.
+template <typename F>
+void for_each_segment(const GroupTableView& tv, int64_t lo, int64_t hi, F&& f) {
+  int s = static_cast<int>(
+      std::upper_bound(tv.seg_end, tv.seg_end + tv.S, lo) - tv.seg_end);
+  while (lo < hi && s < tv.S) {
+    const int64_t e = std::min(tv.seg_end[s], hi);
+    f(lo, e, static_cast<int>(tv.seg_group[s]));
+    lo = e;
+    ++s;
+  }
+}
+
+}  // namespace
+
 void Engine::grad_clip_coef(uintptr_t grad, bool grad_bf16, int64_t n,
                             double max_norm, uintptr_t scratch,
                             uintptr_t state, uintptr_t stream) {
@@ -1750,55 +1834,90 @@ void Engine::grad_clip_coef(uintptr_t grad, bool grad_bf16, int64_t n,
 
 void Engine::fused_sgd(uintptr_t mom, uintptr_t grad, double lr,
                        double momentum, uintptr_t stream,
-                       uintptr_t clip_state) {
+                       uintptr_t clip_state, uintptr_t groups) {
   const ClipState* clip = reinterpret_cast<const ClipState*>(clip_state);
+  const void* table = reinterpret_cast<const void*>(groups);
   std::shared_lock<std::shared_mutex> ug(user_m_);
   void* d[3];
   for (int i = 0; i < 3; ++i)
     d[i] = links_[i].provisioned ? links_[i].delta : nullptr;
   if (gpu()) {
-    hip_fused_sgd(reinterpret_cast<float*>(mom),
-                  reinterpret_cast<const float*>(grad), static_cast<float>(lr),
-                  static_cast<float>(momentum), n_, values_, d[0], d[1], d[2],
-                  cfg_.delta_bf16, reinterpret_cast<hipStream_t>(stream),
-                  clip);
+    if (table) {
+      hip_fused_sgd_grouped(
+          reinterpret_cast<float*>(mom), reinterpret_cast<const float*>(grad),
+          static_cast<float>(lr), static_cast<float>(momentum), n_, values_,
+          d[0], d[1], d[2], cfg_.delta_bf16,
+          reinterpret_cast<hipStream_t>(stream), clip, table);
+    } else {
+      hip_fused_sgd(reinterpret_cast<float*>(mom),
+                    reinterpret_cast<const float*>(grad),
+                    static_cast<float>(lr), static_cast<float>(momentum), n_,
+                    values_, d[0], d[1], d[2], cfg_.delta_bf16,
+                    reinterpret_cast<hipStream_t>(stream), clip);
+    }
   } else {
     if (clip && clip->skip) return;  // nothing staged: no sender to wake
     const float coef = clip ? clip->coef : 1.0f;
     float* m = reinterpret_cast<float*>(mom);
     const float* g = reinterpret_cast<const float*>(grad);
-    cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+    // neg_lr: -lr of the elements [lo, hi)
+    auto run = [&](int64_t lo, int64_t hi, float neg_lr) {
       for (int64_t i = lo; i < hi; ++i) {
         float gi = clip ? mul_uncontracted_f32(g[i], coef) : g[i];
         float mm = static_cast<float>(momentum) * m[i] + gi;
         m[i] = mm;
-        float u = static_cast<float>(-lr) * mm;
+        float u = neg_lr * mm;
         if (u == 0.0f) continue;
         atomic_add_f32(values_ + i, u);
         for (int k = 0; k < 3; ++k)
           if (d[k]) atomic_add_f32(fdelta(d[k]) + i, u);
       }
-    });
+    };
+    if (table) {
+      const GroupTableView tv = checked_group_view(table, n_);
+      cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+        for_each_segment(tv, lo, hi, [&](int64_t a, int64_t b, int grp) {
+          run(a, b, -mul_uncontracted_f32(static_cast<float>(lr),
+                                          tv.lr_scale[grp]));
+        });
+      });
+    } else {
+      cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+        run(lo, hi, static_cast<float>(-lr));
+      });
+    }
   }
   notify_all_dirty();
 }
 
 void Engine::fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16,
                             uintptr_t shadow_bf16, double lr, double momentum,
-                            uintptr_t stream, uintptr_t clip_state) {
+                            uintptr_t stream, uintptr_t clip_state,
+                            uintptr_t groups) {
   if (!gpu())
     throw std::runtime_error("fused_sgd_bf16 is a GPU-only path");
   std::shared_lock<std::shared_mutex> ug(user_m_);
   void* d[3];
   for (int i = 0; i < 3; ++i)
     d[i] = links_[i].provisioned ? links_[i].delta : nullptr;
-  hip_fused_sgd_bf16(reinterpret_cast<float*>(mom),
-                     reinterpret_cast<const uint16_t*>(grad_bf16),
-                     reinterpret_cast<uint16_t*>(shadow_bf16),
-                     static_cast<float>(lr), static_cast<float>(momentum), n_,
-                     values_, d[0], d[1], d[2], cfg_.delta_bf16,
-                     reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const ClipState*>(clip_state));
+  if (groups) {
+    hip_fused_sgd_bf16_grouped(
+        reinterpret_cast<float*>(mom),
+        reinterpret_cast<const uint16_t*>(grad_bf16),
+        reinterpret_cast<uint16_t*>(shadow_bf16), static_cast<float>(lr),
+        static_cast<float>(momentum), n_, values_, d[0], d[1], d[2],
+        cfg_.delta_bf16, reinterpret_cast<hipStream_t>(stream),
+        reinterpret_cast<const ClipState*>(clip_state),
+        reinterpret_cast<const void*>(groups));
+  } else {
+    hip_fused_sgd_bf16(reinterpret_cast<float*>(mom),
+                       reinterpret_cast<const uint16_t*>(grad_bf16),
+                       reinterpret_cast<uint16_t*>(shadow_bf16),
+                       static_cast<float>(lr), static_cast<float>(momentum),
+                       n_, values_, d[0], d[1], d[2], cfg_.delta_bf16,
+                       reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const ClipState*>(clip_state));
+  }
   notify_all_dirty();
 }
 
@@ -1806,8 +1925,9 @@ void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
                          bool grad_bf16, uintptr_t shadow, double lr,
                          double beta1, double beta2, double eps, double wd,
                          int64_t step, uintptr_t stream,
-                         uintptr_t clip_state) {
+                         uintptr_t clip_state, uintptr_t groups) {
   const ClipState* clip = reinterpret_cast<const ClipState*>(clip_state);
+  const void* table = reinterpret_cast<const void*>(groups);
   if (step < 1) throw std::runtime_error("fused_adamw: step must be >= 1");
   if (grad_bf16 && !gpu())
     throw std::runtime_error("bf16 grads are a GPU-only path");
@@ -1821,23 +1941,33 @@ void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
   const float inv_bc2 =
       1.0f / (1.0f - std::pow(b2, static_cast<float>(step)));
   if (gpu()) {
-    hip_fused_adamw(reinterpret_cast<float*>(mom),
-                    reinterpret_cast<float*>(vel),
-                    reinterpret_cast<const void*>(grad), grad_bf16,
-                    reinterpret_cast<uint16_t*>(shadow),
-                    static_cast<float>(lr), b1, b2, static_cast<float>(eps),
-                    static_cast<float>(wd), inv_bc1, inv_bc2, n_, values_,
-                    d[0], d[1], d[2], cfg_.delta_bf16,
-                    reinterpret_cast<hipStream_t>(stream), clip);
+    if (table) {
+      hip_fused_adamw_grouped(
+          reinterpret_cast<float*>(mom), reinterpret_cast<float*>(vel),
+          reinterpret_cast<const void*>(grad), grad_bf16,
+          reinterpret_cast<uint16_t*>(shadow), static_cast<float>(lr), b1, b2,
+          static_cast<float>(eps), inv_bc1, inv_bc2, n_, values_, d[0], d[1],
+          d[2], cfg_.delta_bf16, reinterpret_cast<hipStream_t>(stream), clip,
+          table);
+    } else {
+      hip_fused_adamw(reinterpret_cast<float*>(mom),
+                      reinterpret_cast<float*>(vel),
+                      reinterpret_cast<const void*>(grad), grad_bf16,
+                      reinterpret_cast<uint16_t*>(shadow),
+                      static_cast<float>(lr), b1, b2, static_cast<float>(eps),
+                      static_cast<float>(wd), inv_bc1, inv_bc2, n_, values_,
+                      d[0], d[1], d[2], cfg_.delta_bf16,
+                      reinterpret_cast<hipStream_t>(stream), clip);
+    }
   } else {
     if (clip && clip->skip) return;  // nothing staged: no sender to wake
     const float coef = clip ? clip->coef : 1.0f;
     float* m = reinterpret_cast<float*>(mom);
     float* v = reinterpret_cast<float*>(vel);
     const float* g = reinterpret_cast<const float*>(grad);
-    const float lrf = static_cast<float>(lr), epsf = static_cast<float>(eps);
-    const float wdf = static_cast<float>(wd);
-    cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+    const float epsf = static_cast<float>(eps);
+    // lrf, wdf: rate and decay of the elements [lo, hi)
+    auto run = [&](int64_t lo, int64_t hi, float lrf, float wdf) {
       for (int64_t i = lo; i < hi; ++i) {
         float gi = clip ? mul_uncontracted_f32(g[i], coef) : g[i];
         float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -1852,7 +1982,21 @@ void Engine::fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad,
         for (int k = 0; k < 3; ++k)
           if (d[k]) atomic_add_f32(fdelta(d[k]) + i, u);
       }
-    });
+    };
+    if (table) {
+      const GroupTableView tv = checked_group_view(table, n_);
+      cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+        for_each_segment(tv, lo, hi, [&](int64_t a, int64_t b, int grp) {
+          run(a, b,
+              mul_uncontracted_f32(static_cast<float>(lr), tv.lr_scale[grp]),
+              tv.weight_decay[grp]);
+        });
+      });
+    } else {
+      cpu_pfor(n_, [&](int64_t lo, int64_t hi) {
+        run(lo, hi, static_cast<float>(lr), static_cast<float>(wd));
+      });
+    }
   }
   notify_all_dirty();
 }

@@ -82,16 +82,20 @@ class Engine {
   // wrote, in the engine's memory space.  With skip set the step touches
   // nothing and wakes no sender on the CPU; on the GPU the host cannot know
   // and wakes them as usual.  Otherwise fl32(g * coef) replaces g.
+  // groups (all three steps): 0, or a parameter-group table (common.h,
+  // build_group_table) in the engine's memory space: each segment steps with
+  // fl32(lr * lr_scale[g]) and, for AdamW, weight_decay[g] in place of wd.
   void fused_sgd(uintptr_t mom, uintptr_t grad, double lr, double momentum,
-                 uintptr_t stream, uintptr_t clip_state = 0);
+                 uintptr_t stream, uintptr_t clip_state = 0,
+                 uintptr_t groups = 0);
   void fused_sgd_bf16(uintptr_t mom, uintptr_t grad_bf16, uintptr_t shadow_bf16,
                       double lr, double momentum, uintptr_t stream,
-                      uintptr_t clip_state = 0);
+                      uintptr_t clip_state = 0, uintptr_t groups = 0);
   // shadow==0: fp32 grads, no shadow refresh (grad_bf16 must be false)
   void fused_adamw(uintptr_t mom, uintptr_t vel, uintptr_t grad, bool grad_bf16,
                    uintptr_t shadow, double lr, double beta1, double beta2,
                    double eps, double wd, int64_t step, uintptr_t stream,
-                   uintptr_t clip_state = 0);
+                   uintptr_t clip_state = 0, uintptr_t groups = 0);
   // Global gradient norm and clip coefficient of grad[0, n) into *state (32
   // bytes, common.h ClipState; zeroed once by the caller).  GPU engines:
   // two launches on `stream`, scratch = GRAD_CLIP_MAX_BLOCKS device doubles.

@@ -100,6 +100,30 @@ void hip_fused_adamw(float* mom, float* vel, const void* grad, bool grad_bf16,
                      bool delta_bf16, hipStream_t s,
                      const ClipState* clip = nullptr);
 
+// Parameter-group variants (optim_group_kernels.hip).  `table` is the group
+// table of common.h in device memory (build_group_table; never null here).
+// Element i uses lr_eff = fl32(lr * lr_scale[g]), rounded once, wherever the
+// ungrouped step uses lr, and weight_decay[g] for wd, g being the group of
+// the segment that holds i; everything else, clip included, is the ungrouped
+// step, and the results equal it bit for bit segment by segment.  SGD has
+// no weight decay and reads lr_scale only.
+void hip_fused_sgd_grouped(float* mom, const float* grad, float lr,
+                           float momentum, int64_t n, float* values, void* d1,
+                           void* d2, void* d3, bool delta_bf16, hipStream_t s,
+                           const ClipState* clip, const void* table);
+void hip_fused_sgd_bf16_grouped(float* mom, const uint16_t* grad,
+                                uint16_t* shadow, float lr, float momentum,
+                                int64_t n, float* values, void* d1, void* d2,
+                                void* d3, bool delta_bf16, hipStream_t s,
+                                const ClipState* clip, const void* table);
+void hip_fused_adamw_grouped(float* mom, float* vel, const void* grad,
+                             bool grad_bf16, uint16_t* shadow, float lr,
+                             float beta1, float beta2, float eps,
+                             float inv_bc1, float inv_bc2, int64_t n,
+                             float* values, void* d1, void* d2, void* d3,
+                             bool delta_bf16, hipStream_t s,
+                             const ClipState* clip, const void* table);
+
 // Global-norm gradient clipping (grad_clip_kernels.hip).  One read-only pass
 // over grad (fp32, or bf16 with grad_bf16; aligned to its element size, any
 // n >= 1) sums g*g in fp64 into one partial per block, a one-block kernel

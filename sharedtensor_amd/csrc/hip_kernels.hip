@@ -33,6 +33,7 @@
 #include <string>
 
 #include "hip_api.h"
+#include "optim_step.h"
 
 namespace shamd {
 
@@ -55,62 +56,8 @@ static inline int grid_for(int64_t n) {
 
 // ---------------------------------------------------------------- helpers
 
-__device__ __forceinline__ float bf16_to_f32(uint16_t u) {
-  return __uint_as_float(static_cast<uint32_t>(u) << 16);
-}
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;  // NaN
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round-to-nearest-even
-  return static_cast<uint16_t>(u >> 16);
-}
-
-// a + b rounded on its own.  The optimizers' u = -lr * (...) would otherwise
-// be contracted into the shadow's old + u, which then is no longer the
-// rounding of what atomicAdd(values, u) stored (visible where old ~ -u).
-__device__ __forceinline__ float add_uncontracted(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// g * coef rounded to fp32 on its own (gradient clipping): the optimizers
-// use the rounded product wherever they used g, so a clipped step equals an
-// unclipped step on gradients scaled beforehand, bit for bit.
-__device__ __forceinline__ float mul_uncontracted(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
-// Residual-delta storage policies --------------------------------------
-
-struct DeltaF32 {
-  using T = float;
-  static __device__ __forceinline__ float load(const T* p, int64_t i) {
-    return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  static __device__ __forceinline__ void atomic_add(T* p, int64_t i, float v) {
-    atomicAdd(p + i, v);
-  }
-};
-
-struct DeltaBF16 {
-  using T = uint16_t;
-  static __device__ __forceinline__ float load(const T* p, int64_t i) {
-    return bf16_to_f32(p[i]);
-  }
-  static __device__ __forceinline__ void atomic_add(T* p, int64_t i, float v) {
-    // hardware packed bf16 atomic on the containing (even, odd) pair; the
-    // neighbour lane receives -0.0, the exact identity (x + -0.0 == x for
-    // every x; +0.0 would turn a -0.0 neighbour into +0.0)
-    auto* base = reinterpret_cast<__hip_bfloat162*>(p + (i & ~int64_t(1)));
-    __hip_bfloat16 bv = __float2bfloat16(v);
-    __hip_bfloat16 bz = __float2bfloat16(-0.0f);
-    __hip_bfloat162 val = (i & 1) ? __hip_bfloat162(bz, bv)
-                                  : __hip_bfloat162(bv, bz);
-    unsafeAtomicAdd(base, val);
-  }
-};
+// bf16 conversions, add/mul_uncontracted and the residual-delta storage
+// policies (DeltaF32, DeltaBF16) live in optim_step.h.
 
 // Binary search: largest t with poffs[t] <= j.  T is small (1..few hundred)
 // and the array is L2-hot; for T==1 the caller's fast path skips this.
@@ -504,12 +451,8 @@ __global__ void k_snapshot_capture(const float* __restrict__ values,
 // Otherwise the gradient is fl32(g * coef).  Without CLIP the pointer is
 // unused and the kernel is what it was before clipping existed.
 //
-// The moment updates spell out which product is fused into the sum and
-// which is rounded on its own.  Left to the compiler, the choice differed
-// between instantiations (a packed multiply instead of the FMA once g was
-// itself a product), and a clipped step was no longer the unclipped step on
-// scaled gradients.  The forms below are the ones the compiler had picked
-// for the kernels without clipping, so those compute what they always did.
+// The per-element bodies (optim_step.h) are shared with the parameter-group
+// kernels of optim_group_kernels.hip.
 template <typename DP, bool CLIP>
 __global__ void k_fused_sgd(float* __restrict__ mom,
                             const float* __restrict__ grad, float lr,
@@ -523,14 +466,8 @@ __global__ void k_fused_sgd(float* __restrict__ mom,
   }
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += gstride) {
-    float g = CLIP ? mul_uncontracted(grad[i], coef) : grad[i];
-    float m = fmaf(momentum, mom[i], g);
-    mom[i] = m;
-    float u = -lr * m;
-    if (values) atomicAdd(values + i, u);
-    if (d1) DP::atomic_add(d1, i, u);
-    if (d2) DP::atomic_add(d2, i, u);
-    if (d3) DP::atomic_add(d3, i, u);
+    sgd_element<DP, CLIP>(i, mom, grad, lr, momentum, coef, values, d1, d2,
+                          d3);
   }
 }
 
@@ -553,16 +490,8 @@ __global__ void k_fused_sgd_bf16(float* __restrict__ mom,
   }
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += gstride) {
-    float g = bf16_to_f32(grad[i]);
-    if (CLIP) g = mul_uncontracted(g, coef);
-    float m = fmaf(momentum, mom[i], g);
-    mom[i] = m;
-    float u = -lr * m;
-    float old = atomicAdd(values + i, u);
-    shadow[i] = f32_to_bf16(add_uncontracted(old, u));
-    if (d1) DP::atomic_add(d1, i, u);
-    if (d2) DP::atomic_add(d2, i, u);
-    if (d3) DP::atomic_add(d3, i, u);
+    sgd_bf16_element<DP, CLIP>(i, mom, grad, shadow, lr, momentum, coef,
+                               values, d1, d2, d3);
   }
 }
 
@@ -728,11 +657,6 @@ void hip_add_delta_scatter(const void* src_delta, bool delta_bf16, int64_t n,
 // master weight (torch.optim.AdamW semantics), fp32 m/v state, update
 // applied to the replica with atomicAdd (concurrent gossip folds in) and
 // staged into every link residual.  inv_bc1/2 = 1/(1-beta^t) host-side.
-__device__ __forceinline__ float gval(const float* g, int64_t i) { return g[i]; }
-__device__ __forceinline__ float gval(const uint16_t* g, int64_t i) {
-  return bf16_to_f32(g[i]);
-}
-
 template <typename DP, typename GT, bool CLIP>
 __global__ void k_fused_adamw(float* __restrict__ mom, float* __restrict__ vel,
                               const GT* __restrict__ grad,
@@ -750,21 +674,9 @@ __global__ void k_fused_adamw(float* __restrict__ mom, float* __restrict__ vel,
   int64_t gstride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gstride) {
-    float g = gval(grad, i);
-    if (CLIP) g = mul_uncontracted(g, coef);
-    float m = fmaf(1.f - beta1, g, mul_uncontracted(beta1, mom[i]));
-    mom[i] = m;
-    float v = fmaf(g, mul_uncontracted(1.f - beta2, g),
-                   mul_uncontracted(beta2, vel[i]));
-    vel[i] = v;
-    float w = __hip_atomic_load(values + i, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_AGENT);
-    float u = -lr * (m * inv_bc1 / (sqrtf(v * inv_bc2) + eps) + wd * w);
-    float old = atomicAdd(values + i, u);
-    if (shadow) shadow[i] = f32_to_bf16(add_uncontracted(old, u));
-    if (d1) DP::atomic_add(d1, i, u);
-    if (d2) DP::atomic_add(d2, i, u);
-    if (d3) DP::atomic_add(d3, i, u);
+    adamw_element<DP, GT, CLIP>(i, mom, vel, grad, shadow, lr, beta1, beta2,
+                                eps, wd, inv_bc1, inv_bc2, coef, values, d1,
+                                d2, d3);
   }
 }
 

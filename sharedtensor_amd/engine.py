@@ -84,6 +84,7 @@ class _SharedBase:
         self._closed = False
         self._clip_state = None      # allocated by the first grad_clip_coef
         self._clip_scratch = None
+        self._group_shapes = {}      # table data_ptr -> (S, G, table)
 
         msg = _core.msg_bytes(cfg)
         self.values = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -221,27 +222,97 @@ class _SharedBase:
                             "grad_clip_coef returned")
         return clip_state.data_ptr()
 
+    # -- parameter groups --------------------------------------------------
+    def make_group_table(self, seg_sizes: Sequence[int],
+                         seg_group: Sequence[int],
+                         lr_scale: Sequence[float],
+                         weight_decay: Sequence[float]) -> torch.Tensor:
+        """Parameter-group table for the fused steps' `groups` argument: the
+        flat buffer as consecutive segments of `seg_sizes` elements, segment
+        s in group `seg_group[s]`, group g stepping with the rate
+        fl32(lr * lr_scale[g]) and (AdamW) the decay weight_decay[g].
+
+        Validated and coalesced (adjacent segments of one group merge) by
+        _core.build_group_table, then placed on the engine's device as int32
+        words.  Layout (csrc/common.h): i64 n | i32 S | i32 G | i64
+        seg_end[S] | i32 seg_group[S] | f32 lr_scale[G] | f32
+        weight_decay[G].  ValueError unless the sizes are positive and sum
+        to n, group indices are in range, the per-group values are finite
+        and >= 0, there is at least one group, and at most
+        _core.GROUP_MAX_SEGMENTS segments remain after merging."""
+        sizes = [int(x) for x in seg_sizes]
+        if sum(sizes) != self.n:
+            raise ValueError(f"segments cover {sum(sizes)} elements, the "
+                             f"tensor has {self.n}")
+        ends, end = [], 0
+        for x in sizes:
+            end += x
+            ends.append(end)
+        words = _core.build_group_table(self.n, ends,
+                                        [int(g) for g in seg_group],
+                                        [float(x) for x in lr_scale],
+                                        [float(x) for x in weight_decay])
+        table = torch.tensor(words, dtype=torch.int32).to(self.device)
+        self._group_shapes[table.data_ptr()] = (int(words[2]), int(words[3]),
+                                                table)
+        return table
+
+    def _groups_ptr(self, groups: Optional[torch.Tensor]) -> int:
+        if groups is None:
+            return 0
+        if (not isinstance(groups, torch.Tensor)
+                or self._group_shapes.get(groups.data_ptr(),
+                                          (0, 0, None))[2] is not groups):
+            raise TypeError("groups must be a table that this object's "
+                            "make_group_table returned")
+        return groups.data_ptr()
+
+    def update_group_table(self, table: torch.Tensor,
+                           lr_scale: Optional[Sequence[float]] = None,
+                           weight_decay: Optional[Sequence[float]] = None):
+        """Rewrites the per-group values of `table` (all G of either kind).
+        The write is ordered on the engine's stream like the fused steps: a
+        step queued earlier still reads the old values."""
+        self._groups_ptr(table)
+        S, G, _ = self._group_shapes[table.data_ptr()]
+        for k, vals in enumerate((lr_scale, weight_decay)):
+            if vals is None:
+                continue
+            v = torch.tensor([float(x) for x in vals], dtype=torch.float32)
+            if v.numel() != G:
+                raise ValueError(f"expected {G} per-group values")
+            if not bool((torch.isfinite(v) & (v >= 0)).all()):
+                raise ValueError("lr_scale and weight_decay must be finite "
+                                 "and >= 0")
+            at = 4 + 3 * S + k * G
+            table[at:at + G].copy_(v.view(torch.int32))
+
     def fused_sgd_step(self, momentum_buf: torch.Tensor, grad: torch.Tensor,
                        lr: float, momentum: float = 0.9,
-                       clip_state: Optional[torch.Tensor] = None):
+                       clip_state: Optional[torch.Tensor] = None,
+                       groups: Optional[torch.Tensor] = None):
         """m = mu*m + g; u = -lr*m; {replica, link deltas} += u — one fused
         HBM pass (HIP kernel k_fused_sgd) instead of optimizer + addFromTensor.
         With `clip_state` (see grad_clip_coef) g is fl32(g * coef), or the
-        step changes nothing when the state says skip."""
+        step changes nothing when the state says skip.  With `groups` (see
+        make_group_table) each segment steps with fl32(lr * lr_scale[g]),
+        still in one pass (k_fused_sgd_grp); SGD has no weight decay."""
         if momentum_buf.numel() != self.n or grad.numel() != self.n:
             raise ValueError("size mismatch")
         self._eng.fused_sgd(momentum_buf.data_ptr(), grad.data_ptr(),
                             float(lr), float(momentum), self._stream(),
-                            self._clip_ptr(clip_state))
+                            self._clip_ptr(clip_state),
+                            self._groups_ptr(groups))
 
     def fused_sgd_bf16_step(self, momentum_buf: torch.Tensor,
                             grad_bf16: torch.Tensor, shadow_bf16: torch.Tensor,
                             lr: float, momentum: float = 0.9,
-                            clip_state: Optional[torch.Tensor] = None):
+                            clip_state: Optional[torch.Tensor] = None,
+                            groups: Optional[torch.Tensor] = None):
         """Mixed-precision fused step: bf16 grads in, fp32 master updated,
         bf16 shadow params refreshed, link deltas staged — one HBM pass
-        (HIP kernel k_fused_sgd_bf16).  `clip_state`: as fused_sgd_step; the
-        scaled gradient stays fp32."""
+        (HIP kernel k_fused_sgd_bf16).  `clip_state`, `groups`: as
+        fused_sgd_step; the scaled gradient stays fp32."""
         if grad_bf16.dtype != torch.bfloat16 or shadow_bf16.dtype != torch.bfloat16:
             raise TypeError("grad/shadow must be bfloat16")
         if not (momentum_buf.numel() == grad_bf16.numel()
@@ -250,18 +321,23 @@ class _SharedBase:
         self._eng.fused_sgd_bf16(momentum_buf.data_ptr(), grad_bf16.data_ptr(),
                                  shadow_bf16.data_ptr(), float(lr),
                                  float(momentum), self._stream(),
-                                 self._clip_ptr(clip_state))
+                                 self._clip_ptr(clip_state),
+                                 self._groups_ptr(groups))
 
     def fused_adamw_step(self, mom: torch.Tensor, vel: torch.Tensor,
                          grad: torch.Tensor, step: int, lr: float,
                          betas=(0.9, 0.999), eps: float = 1e-8,
                          weight_decay: float = 0.0,
-                         clip_state: Optional[torch.Tensor] = None):
+                         clip_state: Optional[torch.Tensor] = None,
+                         groups: Optional[torch.Tensor] = None):
         """torch.optim.AdamW-semantics update feeding the shared tensor:
         fp32 m/v, decoupled weight decay on the pre-update master weight,
         update applied to the replica AND staged into every link delta in
         one HBM pass (HIP kernel k_fused_adamw).  `clip_state`: as
-        fused_sgd_step; a skipped step leaves m, v and the weights alone."""
+        fused_sgd_step; a skipped step leaves m, v and the weights alone.
+        `groups` (see make_group_table): each segment steps with
+        fl32(lr * lr_scale[g]) and weight_decay[g]; `weight_decay` is then
+        unused (HIP kernel k_fused_adamw_grp, still one pass)."""
         if not (mom.numel() == vel.numel() == grad.numel() == self.n):
             raise ValueError("size mismatch")
         if grad.dtype != torch.float32:
@@ -271,17 +347,20 @@ class _SharedBase:
                               False, 0, float(lr), float(betas[0]),
                               float(betas[1]), float(eps),
                               float(weight_decay), int(step), self._stream(),
-                              self._clip_ptr(clip_state))
+                              self._clip_ptr(clip_state),
+                              self._groups_ptr(groups))
 
     def fused_adamw_bf16_step(self, mom: torch.Tensor, vel: torch.Tensor,
                               grad_bf16: torch.Tensor,
                               shadow_bf16: torch.Tensor, step: int, lr: float,
                               betas=(0.9, 0.999), eps: float = 1e-8,
                               weight_decay: float = 0.0,
-                              clip_state: Optional[torch.Tensor] = None):
+                              clip_state: Optional[torch.Tensor] = None,
+                              groups: Optional[torch.Tensor] = None):
         """Mixed-precision fused AdamW: bf16 grads in, fp32 master updated,
         bf16 shadow params refreshed (folding concurrent gossip), link
-        deltas staged — one HBM pass.  `clip_state`: as fused_adamw_step."""
+        deltas staged — one HBM pass.  `clip_state`, `groups`: as
+        fused_adamw_step."""
         if grad_bf16.dtype != torch.bfloat16 or shadow_bf16.dtype != torch.bfloat16:
             raise TypeError("grad/shadow must be bfloat16")
         if not (mom.numel() == vel.numel() == grad_bf16.numel()
@@ -292,7 +371,8 @@ class _SharedBase:
                               shadow_bf16.data_ptr(), float(lr),
                               float(betas[0]), float(betas[1]), float(eps),
                               float(weight_decay), int(step), self._stream(),
-                              self._clip_ptr(clip_state))
+                              self._clip_ptr(clip_state),
+                              self._groups_ptr(groups))
 
     # -- observability -----------------------------------------------------
     def stats(self) -> dict:
