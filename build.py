@@ -31,6 +31,7 @@ SOURCES = [
     "add_ln_kernels.hip",
     "add_rms_kernels.hip",
     "ce_kernels.hip",
+    "ce_opts_kernels.hip",
     "gelu_kernels.hip",
     "bias_grad_kernels.hip",
     "swiglu_kernels.hip",
@@ -38,7 +39,7 @@ SOURCES = [
     "bindings.cpp",
 ]
 
-HEADERS = ["common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "optim_step.h",
+HEADERS = ["ce_common.h", "common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "optim_step.h",
            "rccl_transport.h"]
 
 

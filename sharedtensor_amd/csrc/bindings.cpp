@@ -476,6 +476,78 @@ PYBIND11_MODULE(_core, m) {
   });
   m.def("ce_fwd_grad_max_v", &hip_ce_fwd_grad_max_v);
 
+  // fused bf16 cross-entropy with ignore_index / label smoothing / z-loss
+  // (ce_opts_kernels.hip).  state: 16 device bytes (hip_api.h CeOptState),
+  // written by ce_opts_scan.  ValueError for options out of range.
+  m.attr("CE_OPT_STATE_BYTES") = static_cast<int>(sizeof(CeOptState));
+  m.def("ce_opts_scan", [](uintptr_t targets, int64_t R, int64_t V,
+                           int32_t ignore_index, bool has_ignore,
+                           uintptr_t state, uintptr_t stream) {
+    hip_ce_opts_scan(reinterpret_cast<const int32_t*>(targets), R, V,
+                     CeOpts{ignore_index, has_ignore, 0.f, 0.f},
+                     reinterpret_cast<CeOptState*>(state),
+                     reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("targets"), py::arg("R"), py::arg("V"), py::arg("ignore_index"),
+     py::arg("has_ignore"), py::arg("state"), py::arg("stream"));
+  m.def("ce_opts_fwd_grad", [](uintptr_t logits, uintptr_t targets,
+                               uintptr_t loss, uintptr_t row_lse,
+                               uintptr_t dlogits, uintptr_t state, int64_t R,
+                               int64_t V, int32_t ignore_index,
+                               bool has_ignore, double label_smoothing,
+                               double z_loss, uintptr_t stream) {
+    hip_ce_opts_fwd_grad(reinterpret_cast<const void*>(logits),
+                         reinterpret_cast<const int32_t*>(targets),
+                         reinterpret_cast<float*>(loss),
+                         reinterpret_cast<float*>(row_lse),
+                         reinterpret_cast<void*>(dlogits),
+                         reinterpret_cast<const CeOptState*>(state),
+                         CeOpts{ignore_index, has_ignore,
+                                static_cast<float>(label_smoothing),
+                                static_cast<float>(z_loss)},
+                         R, V, reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("logits"), py::arg("targets"), py::arg("loss"),
+     py::arg("row_lse"), py::arg("dlogits"), py::arg("state"), py::arg("R"),
+     py::arg("V"), py::arg("ignore_index"), py::arg("has_ignore"),
+     py::arg("label_smoothing"), py::arg("z_loss"), py::arg("stream"));
+  m.def("ce_opts_fwd", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,
+                          uintptr_t row_lse, int64_t R, int64_t V,
+                          int32_t ignore_index, bool has_ignore,
+                          double label_smoothing, double z_loss,
+                          uintptr_t stream) {
+    hip_ce_opts_fwd(reinterpret_cast<const void*>(logits),
+                    reinterpret_cast<const int32_t*>(targets),
+                    reinterpret_cast<float*>(loss),
+                    reinterpret_cast<float*>(row_lse),
+                    CeOpts{ignore_index, has_ignore,
+                           static_cast<float>(label_smoothing),
+                           static_cast<float>(z_loss)},
+                    R, V, reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("logits"), py::arg("targets"), py::arg("loss"),
+     py::arg("row_lse"), py::arg("R"), py::arg("V"), py::arg("ignore_index"),
+     py::arg("has_ignore"), py::arg("label_smoothing"), py::arg("z_loss"),
+     py::arg("stream"));
+  m.def("ce_opts_bwd", [](uintptr_t logits, uintptr_t targets,
+                          uintptr_t row_lse, uintptr_t dlogits,
+                          uintptr_t gscale_dev, uintptr_t state, int64_t R,
+                          int64_t V, int32_t ignore_index, bool has_ignore,
+                          double label_smoothing, double z_loss,
+                          uintptr_t stream, bool skip_if_unit) {
+    hip_ce_opts_bwd(reinterpret_cast<const void*>(logits),
+                    reinterpret_cast<const int32_t*>(targets),
+                    reinterpret_cast<const float*>(row_lse),
+                    reinterpret_cast<void*>(dlogits),
+                    reinterpret_cast<const float*>(gscale_dev),
+                    reinterpret_cast<const CeOptState*>(state),
+                    CeOpts{ignore_index, has_ignore,
+                           static_cast<float>(label_smoothing),
+                           static_cast<float>(z_loss)},
+                    R, V, skip_if_unit, reinterpret_cast<hipStream_t>(stream));
+  }, py::arg("logits"), py::arg("targets"), py::arg("row_lse"),
+     py::arg("dlogits"), py::arg("gscale_dev"), py::arg("state"), py::arg("R"),
+     py::arg("V"), py::arg("ignore_index"), py::arg("has_ignore"),
+     py::arg("label_smoothing"), py::arg("z_loss"), py::arg("stream"),
+     py::arg("skip_if_unit") = false);
+
   // fused bf16 LayerNorm (pointers are bf16 unless named mean/rstd/dgamma/
   // dbeta, which are fp32)
   m.def("ln_fwd", [](uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t y,

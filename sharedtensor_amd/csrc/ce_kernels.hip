@@ -20,157 +20,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "ce_common.h"  // device helpers shared with ce_opts_kernels.hip
 #include "hip_api.h"
 
 namespace shamd {
-
-#define HIP_CHECK_CE(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ float ce_bf16_to_f32(uint16_t u) {
-  return __uint_as_float(static_cast<uint32_t>(u) << 16);
-}
-
-static __device__ __forceinline__ uint16_t ce_f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-
-static __device__ __forceinline__ float ce_pair_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float ce_pair_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint32_t ce_pair_pack(float lo, float hi) {
-  return static_cast<uint32_t>(ce_f32_to_bf16(lo)) |
-         (static_cast<uint32_t>(ce_f32_to_bf16(hi)) << 16);
-}
-
-constexpr int CE_BLOCK = 256;  // 4 waves (fwd: measured vs 512, see launcher)
-
-// block-wide sum (BLK/64-wave block): wave shfl tree + LDS combine
-template <int BLK>
-static __device__ __forceinline__ float block_sum(float v, float* ldsw) {
-  for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w, 64);
-  int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) ldsw[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < BLK / 64; ++i) t += ldsw[i];
-  __syncthreads();
-  return t;
-}
-
-template <int BLK>
-static __device__ __forceinline__ float block_max(float v, float* ldsw) {
-  for (int w = 32; w > 0; w >>= 1) v = fmaxf(v, __shfl_down(v, w, 64));
-  int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) ldsw[wave] = v;
-  __syncthreads();
-  float t = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < BLK / 64; ++i) t = fmaxf(t, ldsw[i]);
-  __syncthreads();
-  return t;
-}
-
-// Rows are only 2-byte aligned when V is odd (GPT-2: V = 50257), so each
-// row is processed as [head: up to 7 elems | body: 16-byte-aligned chunks of
-// 8 elems | tail: up to 7 elems].  The body moves with 16-byte loads and
-// stores; the at most 14 edge elements go one by one, edge e to "edge
-// thread" e, so nothing outside the row is ever read or written.
-struct CeRow {
-  int head, tail;
-  int64_t nbody;  // 16-byte chunks
-};
-
-static __device__ __forceinline__ CeRow ce_row_split(const uint16_t* xr,
-                                                     int64_t V) {
-  CeRow g;
-  int h = static_cast<int>((16 - (reinterpret_cast<uintptr_t>(xr) & 15)) & 15) >> 1;
-  g.head = h < V ? h : static_cast<int>(V);
-  g.nbody = (V - g.head) >> 3;
-  g.tail = static_cast<int>(V - g.head - (g.nbody << 3));
-  return g;
-}
-
-// row index of edge element e (e < head + tail)
-static __device__ __forceinline__ int64_t ce_edge_index(const CeRow& g, int e,
-                                                        int64_t V) {
-  return e < g.head ? e : V - g.tail + (e - g.head);
-}
-
-static __device__ __forceinline__ float ce_max8(const uint4& u) {
-  float a = fmaxf(fmaxf(ce_pair_lo(u.x), ce_pair_hi(u.x)),
-                  fmaxf(ce_pair_lo(u.y), ce_pair_hi(u.y)));
-  float b = fmaxf(fmaxf(ce_pair_lo(u.z), ce_pair_hi(u.z)),
-                  fmaxf(ce_pair_lo(u.w), ce_pair_hi(u.w)));
-  return fmaxf(a, b);
-}
-
-static __device__ __forceinline__ float ce_expsum8(const uint4& u, float m) {
-  float a = __expf(ce_pair_lo(u.x) - m) + __expf(ce_pair_hi(u.x) - m);
-  float b = __expf(ce_pair_lo(u.y) - m) + __expf(ce_pair_hi(u.y) - m);
-  float c = __expf(ce_pair_lo(u.z) - m) + __expf(ce_pair_hi(u.z) - m);
-  float d = __expf(ce_pair_lo(u.w) - m) + __expf(ce_pair_hi(u.w) - m);
-  return (a + b) + (c + d);
-}
-
-static __device__ __forceinline__ float ce_grad1(float x, float lse,
-                                                 float gscale, bool hot) {
-  return gscale * (__expf(x - lse) - (hot ? 1.f : 0.f));
-}
-
-// gradient of one pair; d = (target index) - (index of the pair's low elem)
-static __device__ __forceinline__ uint32_t ce_grad_pair(uint32_t p, float lse,
-                                                        float gscale, int d) {
-  return ce_pair_pack(ce_grad1(ce_pair_lo(p), lse, gscale, d == 0),
-                      ce_grad1(ce_pair_hi(p), lse, gscale, d == 1));
-}
-
-// gradient of one body chunk; d = (target index) - (index of its first elem)
-static __device__ __forceinline__ uint4 ce_grad8(const uint4& u, float lse,
-                                                 float gscale, int d) {
-  uint4 o;
-  o.x = ce_grad_pair(u.x, lse, gscale, d);
-  o.y = ce_grad_pair(u.y, lse, gscale, d - 2);
-  o.z = ce_grad_pair(u.z, lse, gscale, d - 4);
-  o.w = ce_grad_pair(u.w, lse, gscale, d - 6);
-  return o;
-}
-
-// target offset of a chunk as an int; anything outside [0, 8) is "not here"
-static __device__ __forceinline__ int ce_clamp_d(int64_t d) {
-  return d < -8 ? -8 : (d > 8 ? 8 : static_cast<int>(d));
-}
-
-// dlogits rows have the logits' 16-byte phase whenever both buffers start on
-// a 16-byte boundary (every torch allocation); a view at another offset
-// stores its body element-wise instead
-static __device__ __forceinline__ void ce_store8(uint16_t* dst, const uint4& o,
-                                                 bool aligned) {
-  if (aligned) {
-    *reinterpret_cast<uint4*>(dst) = o;
-  } else {
-    dst[0] = static_cast<uint16_t>(o.x);
-    dst[1] = static_cast<uint16_t>(o.x >> 16);
-    dst[2] = static_cast<uint16_t>(o.y);
-    dst[3] = static_cast<uint16_t>(o.y >> 16);
-    dst[4] = static_cast<uint16_t>(o.z);
-    dst[5] = static_cast<uint16_t>(o.z >> 16);
-    dst[6] = static_cast<uint16_t>(o.w);
-    dst[7] = static_cast<uint16_t>(o.w >> 16);
-  }
-}
 
 template <int BLK>
 __global__ void k_ce_fwd(const uint16_t* __restrict__ logits,
@@ -360,12 +213,7 @@ void hip_ce_fwd(const void* logits, const int32_t* targets, float* loss,
   HIP_CHECK_CE(hipGetLastError());
 }
 
-// register capacity of the k_ce_fwd_grad instantiations: 1024 threads x
-// NCHUNK chunks x 8 elements (the <= 7-element head and tail ride on top)
-constexpr int CE_ROW_BLOCK = 1024;
-constexpr int64_t CE_ROW_CAP7 = int64_t(CE_ROW_BLOCK) * 7 * 8;    // GPT-2
-constexpr int64_t CE_ROW_CAP16 = int64_t(CE_ROW_BLOCK) * 16 * 8;  // Llama
-
+// register capacity of the k_ce_fwd_grad instantiations: ce_common.h
 int64_t hip_ce_fwd_grad_max_v() { return CE_ROW_CAP16; }
 
 void hip_ce_fwd_grad(const void* logits, const int32_t* targets, float* loss,

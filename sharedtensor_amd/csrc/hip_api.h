@@ -228,6 +228,48 @@ void hip_ce_fwd_grad(const void* logits, const int32_t* targets, float* loss,
                      float* row_lse, void* dlogits, float inv_r, int64_t R,
                      int64_t V, hipStream_t s);
 
+// Fused cross-entropy with options (ce_opts_kernels.hip).  Row r is valid
+// when targets[r] != ignore_index (if has_ignore) and 0 <= targets[r] < V.
+// Per valid row:
+//   loss_r = (1-eps)*(lse - x_t) + eps*(lse - mean_j x_j) + z*lse^2
+//   dx_j   = g*inv_count*[(1 + 2*z*lse)*softmax_j - (1-eps)*[j==t] - eps/V]
+// An ignored row is never read: loss_r = 0, row_lse = 0, dlogits row = +0.
+// A row with an out-of-range target is treated the same except that its
+// loss_r is NaN.
+//
+// Device state written by hip_ce_opts_scan and read by the other kernels
+// from device memory (no host sync), 16 bytes:
+struct CeOptState {
+  float inv_count;   // 1.0f / n_valid, IEEE division (+inf when n_valid == 0)
+  uint32_t n_valid;  // rows that count
+  uint32_t n_bad;    // rows whose target is out of range and not ignored
+  uint32_t pad;
+};
+struct CeOpts {
+  int32_t ignore_index;
+  bool has_ignore;
+  float eps;  // label smoothing, [0, 1)
+  float z;    // z-loss weight, >= 0
+};
+// one block, no atomics, fixed reduction order: bitwise reproducible
+void hip_ce_opts_scan(const int32_t* targets, int64_t R, int64_t V,
+                      const CeOpts& o, CeOptState* state, hipStream_t s);
+// one-pass fwd + grad (upstream gradient 1); V <= hip_ce_fwd_grad_max_v()
+void hip_ce_opts_fwd_grad(const void* logits, const int32_t* targets,
+                          float* loss, float* row_lse, void* dlogits,
+                          const CeOptState* state, const CeOpts& o, int64_t R,
+                          int64_t V, hipStream_t s);
+// stats-only forward (no_grad, or V beyond the register capacity)
+void hip_ce_opts_fwd(const void* logits, const int32_t* targets, float* loss,
+                     float* row_lse, const CeOpts& o, int64_t R, int64_t V,
+                     hipStream_t s);
+// full backward from logits and row_lse; skip_if_unit as hip_ce_bwd
+void hip_ce_opts_bwd(const void* logits, const int32_t* targets,
+                     const float* row_lse, void* dlogits,
+                     const float* gscale_dev, const CeOptState* state,
+                     const CeOpts& o, int64_t R, int64_t V, bool skip_if_unit,
+                     hipStream_t s);
+
 // Fused bf16 SwiGLU (swiglu_kernels.hip): y = silu(x1)*x3 one kernel each
 // way; n must be a multiple of 8, buffers 16-byte aligned (uint4 loads).
 void hip_swiglu_fwd(const void* x1, const void* x3, void* y, int64_t n,

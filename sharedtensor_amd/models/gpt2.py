@@ -13,6 +13,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -27,6 +28,10 @@ class GPT2Config:
     n_embd: int = 768
     block_size: int = 1024
     dropout: float = 0.0
+    # loss options (ops/fused_ce.py); the defaults are the plain mean
+    ignore_index: Optional[int] = None
+    label_smoothing: float = 0.0
+    z_loss: float = 0.0
 
     @classmethod
     def small(cls):  # 124M — the benchmark config
@@ -247,6 +252,19 @@ class GPT2(nn.Module):
             return logits, None
         flat = logits.view(-1, logits.size(-1))
         tgt = targets.reshape(-1)
+        cfg = self.cfg
+        if cfg.ignore_index is not None or cfg.label_smoothing != 0.0 \
+                or cfg.z_loss != 0.0:
+            # cuda/bf16: the fused kernels with the options; every other
+            # path the same semantics in plain torch
+            from ..ops import fused_ce
+            opts = dict(ignore_index=cfg.ignore_index,
+                        label_smoothing=cfg.label_smoothing,
+                        z_loss=cfg.z_loss)
+            if fused_ce.can_use(flat):
+                return logits, fused_ce.fused_cross_entropy(flat, tgt, **opts)
+            return logits, fused_ce.cross_entropy_reference(flat.float(), tgt,
+                                                            **opts)
         if flat.is_cuda and flat.dtype == torch.bfloat16:
             from ..ops import fused_ce
             if fused_ce.can_use(flat):

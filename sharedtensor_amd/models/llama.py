@@ -10,6 +10,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -27,6 +28,10 @@ class LlamaConfig:
     block_size: int = 8192
     rope_theta: float = 500000.0
     norm_eps: float = 1e-5
+    # loss options (ops/fused_ce.py); the defaults are the plain mean
+    ignore_index: Optional[int] = None
+    label_smoothing: float = 0.0
+    z_loss: float = 0.0
 
     @classmethod
     def llama3_8b(cls):
@@ -221,6 +226,10 @@ class Llama(nn.Module):
             return logits, None
         flat = logits.view(-1, logits.size(-1))
         tgt = targets.reshape(-1)
+        cfg = self.cfg
+        if cfg.ignore_index is not None or cfg.label_smoothing != 0.0 \
+                or cfg.z_loss != 0.0:
+            return logits, self._loss_with_options(flat, tgt)
         if flat.is_cuda and flat.dtype == torch.bfloat16 \
                 and os.environ.get("SHTENS_NO_FUSED_CE_LLAMA") != "1":
             # one read of the bf16 logits gives loss and dlogits
@@ -231,6 +240,18 @@ class Llama(nn.Module):
                 return logits, fused_ce.fused_cross_entropy(flat, tgt)
         loss = F.cross_entropy(flat.float(), tgt)
         return logits, loss
+
+    def _loss_with_options(self, flat, tgt):
+        # cuda/bf16: the fused kernels with the options; every other path
+        # (CPU, fp32, the A/B knob) the same semantics in plain torch
+        from ..ops import fused_ce
+        opts = dict(ignore_index=self.cfg.ignore_index,
+                    label_smoothing=self.cfg.label_smoothing,
+                    z_loss=self.cfg.z_loss)
+        if fused_ce.can_use(flat) \
+                and os.environ.get("SHTENS_NO_FUSED_CE_LLAMA") != "1":
+            return fused_ce.fused_cross_entropy(flat, tgt, **opts)
+        return fused_ce.cross_entropy_reference(flat.float(), tgt, **opts)
 
     def num_params(self):
         return sum(p.numel() for p in self.parameters())
