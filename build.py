@@ -39,8 +39,8 @@ SOURCES = [
     "bindings.cpp",
 ]
 
-HEADERS = ["ce_common.h", "common.h", "codec_cpu.h", "engine.h", "gelu_math.h", "hip_api.h", "optim_step.h",
-           "rccl_transport.h"]
+HEADERS = ["ce_common.h", "common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
+           "optim_step.h", "rccl_transport.h"]
 
 
 def pybind11_include():

@@ -24,45 +24,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"  // declaration parity check
 
 namespace shamd {
-
-#define HIP_CHECK_ALN(expr)                                                \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ uint32_t aln_f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round to nearest even
-  return u >> 16;
-}
-
-static __device__ __forceinline__ void aln_unpack(uint2 p, float* v) {
-  v[0] = __uint_as_float(p.x << 16);
-  v[1] = __uint_as_float(p.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(p.y << 16);
-  v[3] = __uint_as_float(p.y & 0xFFFF0000u);
-}
-
-static __device__ __forceinline__ uint2 aln_pack(const float* v) {
-  uint2 p;
-  p.x = aln_f32_to_bf16(v[0]) | (aln_f32_to_bf16(v[1]) << 16);
-  p.y = aln_f32_to_bf16(v[2]) | (aln_f32_to_bf16(v[3]) << 16);
-  return p;
-}
-
-// Butterfly sum over the 64 lanes of a wave; every lane gets the total.
-static __device__ __forceinline__ float aln_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 constexpr int ALN_FWD_THREADS = 256;   // 4 rows per block
 constexpr int ALN_BWD_THREADS = 256;   // 4 rows in flight per block
@@ -97,30 +62,30 @@ __global__ __launch_bounds__(ALN_FWD_THREADS) void k_add_ln_fwd(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       float a[4], d[4];
-      aln_unpack(px[k], a);
-      aln_unpack(pd[k], d);
+      unpack4(px[k], a);
+      unpack4(pd[k], d);
 #pragma unroll
       for (int j = 0; j < 4; ++j) a[j] += d[j];
       if (dbias) {
         float bb[4];
-        aln_unpack(reinterpret_cast<const uint2*>(dbias)[k * 64 + lane], bb);
+        unpack4(reinterpret_cast<const uint2*>(dbias)[k * 64 + lane], bb);
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[j] += bb[j];
       }
       // statistics and y come from the rounded sum, as if x_new had been
       // written by a separate add and read back
-      uint2 o = aln_pack(a);
+      uint2 o = pack4(a);
       xo[k * 64 + lane] = o;
-      aln_unpack(o, v[k]);
+      unpack4(o, v[k]);
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < NV; ++k) aln_unpack(px[k], v[k]);
+    for (int k = 0; k < NV; ++k) unpack4(px[k], v[k]);
   }
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < NV; ++k) s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-  const float m = aln_wave_sum(s) * (1.f / C);
+  const float m = wave_sum(s) * (1.f / C);
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < NV; ++k)
@@ -129,7 +94,7 @@ __global__ __launch_bounds__(ALN_FWD_THREADS) void k_add_ln_fwd(
       float d = v[k][j] - m;
       q += d * d;
     }
-  const float rs = rsqrtf(aln_wave_sum(q) * (1.f / C) + eps);
+  const float rs = rsqrtf(wave_sum(q) * (1.f / C) + eps);
   if (lane == 0) {
     mean[r] = m;
     rstd[r] = rs;
@@ -138,16 +103,16 @@ __global__ __launch_bounds__(ALN_FWD_THREADS) void k_add_ln_fwd(
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     float ww[4], o[4];
-    aln_unpack(reinterpret_cast<const uint2*>(w)[k * 64 + lane], ww);
+    unpack4(reinterpret_cast<const uint2*>(w)[k * 64 + lane], ww);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = (v[k][j] - m) * rs * ww[j];
     if (b) {
       float bb[4];
-      aln_unpack(reinterpret_cast<const uint2*>(b)[k * 64 + lane], bb);
+      unpack4(reinterpret_cast<const uint2*>(b)[k * 64 + lane], bb);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] += bb[j];
     }
-    yr[k * 64 + lane] = aln_pack(o);
+    yr[k * 64 + lane] = pack4(o);
   }
 }
 
@@ -199,9 +164,9 @@ __global__ __launch_bounds__(ALN_BWD_THREADS) void k_add_ln_bwd(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       float d[4], xv[4], ww[4];
-      aln_unpack(pg[k], d);
-      aln_unpack(px[k], xv);
-      aln_unpack(pw[k], ww);
+      unpack4(pg[k], d);
+      unpack4(px[k], xv);
+      unpack4(pw[k], ww);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float h = (xv[j] - m) * rs;
@@ -226,15 +191,15 @@ __global__ __launch_bounds__(ALN_BWD_THREADS) void k_add_ln_bwd(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       float d[4], xv[4], ww[4], o[4];
-      aln_unpack(pg[k], d);
-      aln_unpack(px[k], xv);
-      aln_unpack(pw[k], ww);
+      unpack4(pg[k], d);
+      unpack4(px[k], xv);
+      unpack4(pw[k], ww);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         o[j] = (d[j] * ww[j] - t1 - (xv[j] - m) * rs * t2) * rs;
       if (dres) {
         float rv[4];
-        aln_unpack(pr[k], rv);
+        unpack4(pr[k], rv);
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] += rv[j];
       }
@@ -242,7 +207,7 @@ __global__ __launch_bounds__(ALN_BWD_THREADS) void k_add_ln_bwd(
 #pragma unroll
         for (int j = 0; j < 4; ++j) ad[k][j] += o[j];
       }
-      dxr[k * 64 + lane] = aln_pack(o);
+      dxr[k * 64 + lane] = pack4(o);
     }
   }
   // combine the block's waves in wave order (fixed, so repeatable), then
@@ -302,7 +267,7 @@ __global__ __launch_bounds__(256) void k_add_ln_reduce(
     for (int i = 0; i < 16; ++i) t += red[i][cg];
     const int s = j / C, c = j - s * C;
     uint16_t* out = s == 0 ? o0 : (s == 1 ? o1 : o2);
-    if (out) out[c] = static_cast<uint16_t>(aln_f32_to_bf16(t));
+    if (out) out[c] = f32_to_bf16(t);
   }
 }
 
@@ -312,12 +277,6 @@ bool hip_add_ln_supported(int C) {
 
 int hip_add_ln_max_blocks() { return ALN_MAX_BLOCKS; }
 
-static void aln_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 7u)
-    throw std::runtime_error(std::string("add_ln: ") + what +
-                             " is not 8-byte aligned");
-}
-
 void hip_add_ln_fwd(const void* x, const void* delta, const void* dbias,
                     const void* w, const void* b, void* x_new, void* y,
                     float* mean, float* rstd, int64_t R, int C, float eps,
@@ -325,13 +284,13 @@ void hip_add_ln_fwd(const void* x, const void* delta, const void* dbias,
   if (!hip_add_ln_supported(C)) throw std::runtime_error("add_ln: bad C");
   if (delta && !x_new) throw std::runtime_error("add_ln: delta needs x_new");
   if (dbias && !delta) throw std::runtime_error("add_ln: dbias needs delta");
-  aln_check_align(x, "x");
-  aln_check_align(delta, "delta");
-  aln_check_align(dbias, "delta_bias");
-  aln_check_align(w, "weight");
-  aln_check_align(b, "bias");
-  aln_check_align(x_new, "x_new");
-  aln_check_align(y, "y");
+  check_align(x, 8, "add_ln", "x");
+  check_align(delta, 8, "add_ln", "delta");
+  check_align(dbias, 8, "add_ln", "delta_bias");
+  check_align(w, 8, "add_ln", "weight");
+  check_align(b, 8, "add_ln", "bias");
+  check_align(x_new, 8, "add_ln", "x_new");
+  check_align(y, 8, "add_ln", "y");
   if (R <= 0) return;
   constexpr int rows = ALN_FWD_THREADS / 64;
   const int64_t blocks = (R + rows - 1) / rows;
@@ -347,13 +306,9 @@ void hip_add_ln_fwd(const void* x, const void* delta, const void* dbias,
                        static_cast<uint16_t*>(x_new),
                        static_cast<uint16_t*>(y), mean, rstd, R, eps);
   };
-  switch (C / 256) {
-    case 1: launch(k_add_ln_fwd<1>); break;
-    case 2: launch(k_add_ln_fwd<2>); break;
-    case 3: launch(k_add_ln_fwd<3>); break;
-    default: launch(k_add_ln_fwd<4>); break;
-  }
-  HIP_CHECK_ALN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4>(C / 256,
+                           [&](auto NV) { launch(k_add_ln_fwd<NV()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 // Blocks that fit on the device at once for one instantiation (the grid
@@ -363,13 +318,13 @@ void hip_add_ln_fwd(const void* x, const void* delta, const void* dbias,
 template <typename K>
 static int aln_resident_blocks(K kern, int* cache) {
   int dev = 0;
-  HIP_CHECK_ALN(hipGetDevice(&dev));
+  HIP_CHECK(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) dev = 0;
   if (cache[dev] == 0) {
     int per_cu = 0, cus = 0;
-    HIP_CHECK_ALN(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &per_cu, kern, ALN_BWD_THREADS, 0));
-    HIP_CHECK_ALN(hipDeviceGetAttribute(
+    HIP_CHECK(hipDeviceGetAttribute(
         &cus, hipDeviceAttributeMultiprocessorCount, dev));
     int g = per_cu * cus;
     if (g < 1) g = 1;
@@ -384,11 +339,11 @@ void hip_add_ln_bwd(const void* dy, const void* x_new, const void* w,
                     void* dx_total, void* dgamma, void* dbeta, void* ddbias,
                     float* partial, int64_t R, int C, hipStream_t s) {
   if (!hip_add_ln_supported(C)) throw std::runtime_error("add_ln: bad C");
-  aln_check_align(dy, "dy");
-  aln_check_align(x_new, "x_new");
-  aln_check_align(w, "weight");
-  aln_check_align(d_x_new, "d_x_new");
-  aln_check_align(dx_total, "dx_total");
+  check_align(dy, 8, "add_ln", "dy");
+  check_align(x_new, 8, "add_ln", "x_new");
+  check_align(w, 8, "add_ln", "weight");
+  check_align(d_x_new, 8, "add_ln", "d_x_new");
+  check_align(dx_total, 8, "add_ln", "dx_total");
   if (reinterpret_cast<uintptr_t>(partial) & 15u)
     throw std::runtime_error("add_ln: partials are not 16-byte aligned");
   if (R <= 0) throw std::runtime_error("add_ln: empty input");
@@ -406,28 +361,21 @@ void hip_add_ln_bwd(const void* dy, const void* x_new, const void* w,
                        static_cast<uint16_t*>(dx_total), partial, R);
   };
   const int nv = C / 256;
-  if (ddbias) {
-    switch (nv) {
-      case 1: launch(k_add_ln_bwd<1, true>, cache[0][1]); break;
-      case 2: launch(k_add_ln_bwd<2, true>, cache[1][1]); break;
-      case 3: launch(k_add_ln_bwd<3, true>, cache[2][1]); break;
-      default: launch(k_add_ln_bwd<4, true>, cache[3][1]); break;
-    }
-  } else {
-    switch (nv) {
-      case 1: launch(k_add_ln_bwd<1, false>, cache[0][0]); break;
-      case 2: launch(k_add_ln_bwd<2, false>, cache[1][0]); break;
-      case 3: launch(k_add_ln_bwd<3, false>, cache[2][0]); break;
-      default: launch(k_add_ln_bwd<4, false>, cache[3][0]); break;
-    }
-  }
-  HIP_CHECK_ALN(hipGetLastError());
+  if (ddbias)
+    dispatch_cpt<1, 2, 3, 4>(nv, [&](auto NV) {
+      launch(k_add_ln_bwd<NV(), true>, cache[NV() - 1][1]);
+    });
+  else
+    dispatch_cpt<1, 2, 3, 4>(nv, [&](auto NV) {
+      launch(k_add_ln_bwd<NV(), false>, cache[NV() - 1][0]);
+    });
+  HIP_CHECK(hipGetLastError());
   const int nsc = (ddbias ? 3 : 2) * C;
   hipLaunchKernelGGL(k_add_ln_reduce, dim3(nsc / 16), dim3(256), 0, s, partial,
                      grid, nsc, C, static_cast<uint16_t*>(dgamma),
                      static_cast<uint16_t*>(dbeta),
                      static_cast<uint16_t*>(ddbias));
-  HIP_CHECK_ALN(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

@@ -24,44 +24,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"  // declaration parity check
 
 namespace shamd {
-
-#define HIP_CHECK_ARMS(expr)                                               \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ uint32_t arms_f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round to nearest even
-  return u >> 16;
-}
-
-static __device__ __forceinline__ void arms_unpack(uint4 p, float* v) {
-  v[0] = __uint_as_float(p.x << 16);
-  v[1] = __uint_as_float(p.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(p.y << 16);
-  v[3] = __uint_as_float(p.y & 0xFFFF0000u);
-  v[4] = __uint_as_float(p.z << 16);
-  v[5] = __uint_as_float(p.z & 0xFFFF0000u);
-  v[6] = __uint_as_float(p.w << 16);
-  v[7] = __uint_as_float(p.w & 0xFFFF0000u);
-}
-
-static __device__ __forceinline__ uint4 arms_pack(const float* v) {
-  uint4 p;
-  p.x = arms_f32_to_bf16(v[0]) | (arms_f32_to_bf16(v[1]) << 16);
-  p.y = arms_f32_to_bf16(v[2]) | (arms_f32_to_bf16(v[3]) << 16);
-  p.z = arms_f32_to_bf16(v[4]) | (arms_f32_to_bf16(v[5]) << 16);
-  p.w = arms_f32_to_bf16(v[6]) | (arms_f32_to_bf16(v[7]) << 16);
-  return p;
-}
 
 // Hides a packed register group from the optimiser.  Without it the
 // "recompute after the reduction" below is folded back into values kept
@@ -69,13 +35,6 @@ static __device__ __forceinline__ uint4 arms_pack(const float* v) {
 // loop), which doubles the register count and halves the occupancy.
 static __device__ __forceinline__ void arms_opaque(uint4& p) {
   asm volatile("" : "+v"(p.x), "+v"(p.y), "+v"(p.z), "+v"(p.w));
-}
-
-// Butterfly sum over the 64 lanes of a wave; every lane gets the total.
-static __device__ __forceinline__ float arms_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 constexpr int ARMS_THREADS = 256;      // 4 rows in flight per block
@@ -108,13 +67,13 @@ __global__ __launch_bounds__(ARMS_THREADS) void k_add_rms_fwd(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       float a[8], d[8];
-      arms_unpack(px[k], a);
-      arms_unpack(pd[k], d);
+      unpack8(px[k], a);
+      unpack8(pd[k], d);
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] += d[j];
       // statistics and y come from the rounded sum, as if x_new had been
       // written by a separate add and read back
-      px[k] = arms_pack(a);
+      px[k] = pack8(a);
       xo[k * 64 + lane] = px[k];
     }
   }
@@ -122,21 +81,21 @@ __global__ __launch_bounds__(ARMS_THREADS) void k_add_rms_fwd(
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     float v[8];
-    arms_unpack(px[k], v);
+    unpack8(px[k], v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) q += v[j] * v[j];
   }
-  const float rs = rsqrtf(arms_wave_sum(q) * (1.f / C) + eps);
+  const float rs = rsqrtf(wave_sum(q) * (1.f / C) + eps);
   if (lane == 0) rstd[r] = rs;
   uint4* yr = reinterpret_cast<uint4*>(y + r * C);
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     float v[8], ww[8], o[8];
-    arms_unpack(px[k], v);
-    arms_unpack(reinterpret_cast<const uint4*>(w)[k * 64 + lane], ww);
+    unpack8(px[k], v);
+    unpack8(reinterpret_cast<const uint4*>(w)[k * 64 + lane], ww);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = v[j] * rs * ww[j];
-    yr[k * 64 + lane] = arms_pack(o);
+    yr[k * 64 + lane] = pack8(o);
   }
 }
 
@@ -194,9 +153,9 @@ __attribute__((amdgpu_waves_per_eu(arms_bwd_waves(NV)))) void k_add_rms_bwd(
     for (int k = 0; k < NV; ++k) {
       float d[8], xv[8], ww[8];
       arms_opaque(pw[k]);
-      arms_unpack(pg[k], d);
-      arms_unpack(px[k], xv);
-      arms_unpack(pw[k], ww);
+      unpack8(pg[k], d);
+      unpack8(px[k], xv);
+      unpack8(pw[k], ww);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float h = xv[j] * rs;
@@ -204,7 +163,7 @@ __attribute__((amdgpu_waves_per_eu(arms_bwd_waves(NV)))) void k_add_rms_bwd(
         s += d[j] * ww[j] * h;
       }
     }
-    const float t = arms_wave_sum(s) * (1.f / C);
+    const float t = wave_sum(s) * (1.f / C);
     uint4* dxr = reinterpret_cast<uint4*>(dx + r * C);
     // dy * w and x * rs are recomputed from the packed registers here, not
     // kept across the reduction, which would cost 16 registers per chunk
@@ -214,19 +173,19 @@ __attribute__((amdgpu_waves_per_eu(arms_bwd_waves(NV)))) void k_add_rms_bwd(
       arms_opaque(pg[k]);
       arms_opaque(px[k]);
       arms_opaque(pw[k]);
-      arms_unpack(pg[k], d);
-      arms_unpack(px[k], xv);
-      arms_unpack(pw[k], ww);
+      unpack8(pg[k], d);
+      unpack8(px[k], xv);
+      unpack8(pw[k], ww);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         o[j] = (d[j] * ww[j] - xv[j] * rs * t) * rs;
       if constexpr (DRES) {
         float rv[8];
-        arms_unpack(pr[k], rv);
+        unpack8(pr[k], rv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] += rv[j];
       }
-      dxr[k * 64 + lane] = arms_pack(o);
+      dxr[k * 64 + lane] = pack8(o);
     }
   }
   // combine the block's waves in wave order (fixed, so repeatable), then
@@ -277,7 +236,7 @@ __global__ __launch_bounds__(256) void k_add_rms_reduce(
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) t += red[i][cg];
-    out[j] = static_cast<uint16_t>(arms_f32_to_bf16(t));
+    out[j] = f32_to_bf16(t);
   }
 }
 
@@ -287,12 +246,6 @@ bool hip_add_rms_supported(int C) {
 
 int hip_add_rms_max_blocks() { return ARMS_MAX_BLOCKS; }
 
-static void arms_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 15u)
-    throw std::runtime_error(std::string("add_rms: ") + what +
-                             " is not 16-byte aligned");
-}
-
 void hip_add_rms_fwd(const void* x, const void* delta, const void* w,
                      void* x_new, void* y, float* rstd, int64_t R, int C,
                      float eps, hipStream_t s) {
@@ -300,11 +253,11 @@ void hip_add_rms_fwd(const void* x, const void* delta, const void* w,
   if (delta && !x_new) throw std::runtime_error("add_rms: delta needs x_new");
   if (!x || !w || !y || !rstd)
     throw std::runtime_error("add_rms: null x, weight, y or rstd");
-  arms_check_align(x, "x");
-  arms_check_align(delta, "delta");
-  arms_check_align(w, "weight");
-  arms_check_align(x_new, "x_new");
-  arms_check_align(y, "y");
+  check_align(x, 16, "add_rms", "x");
+  check_align(delta, 16, "add_rms", "delta");
+  check_align(w, 16, "add_rms", "weight");
+  check_align(x_new, 16, "add_rms", "x_new");
+  check_align(y, 16, "add_rms", "y");
   if (R <= 0) return;
   const int64_t blocks = (R + ARMS_WAVES - 1) / ARMS_WAVES;
   if (blocks > 0x7FFFFFFF) throw std::runtime_error("add_rms: R too large");
@@ -317,17 +270,9 @@ void hip_add_rms_fwd(const void* x, const void* delta, const void* w,
                        static_cast<uint16_t*>(x_new),
                        static_cast<uint16_t*>(y), rstd, R, eps);
   };
-  switch (C / 512) {
-    case 1: launch(k_add_rms_fwd<1>); break;
-    case 2: launch(k_add_rms_fwd<2>); break;
-    case 3: launch(k_add_rms_fwd<3>); break;
-    case 4: launch(k_add_rms_fwd<4>); break;
-    case 5: launch(k_add_rms_fwd<5>); break;
-    case 6: launch(k_add_rms_fwd<6>); break;
-    case 7: launch(k_add_rms_fwd<7>); break;
-    default: launch(k_add_rms_fwd<8>); break;
-  }
-  HIP_CHECK_ARMS(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 5, 6, 7, 8>(
+      C / 512, [&](auto NV) { launch(k_add_rms_fwd<NV()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 // Blocks that fit on the device at once for one instantiation (the grid
@@ -337,13 +282,13 @@ void hip_add_rms_fwd(const void* x, const void* delta, const void* w,
 template <typename K>
 static int arms_resident_blocks(K kern, int* cache) {
   int dev = 0;
-  HIP_CHECK_ARMS(hipGetDevice(&dev));
+  HIP_CHECK(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) dev = 0;
   if (cache[dev] == 0) {
     int per_cu = 0, cus = 0;
-    HIP_CHECK_ARMS(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &per_cu, kern, ARMS_THREADS, 0));
-    HIP_CHECK_ARMS(hipDeviceGetAttribute(
+    HIP_CHECK(hipDeviceGetAttribute(
         &cus, hipDeviceAttributeMultiprocessorCount, dev));
     int g = per_cu * cus;
     if (g < 1) g = 1;
@@ -360,12 +305,12 @@ void hip_add_rms_bwd(const void* dy, const void* x_new, const void* w,
   if (!hip_add_rms_supported(C)) throw std::runtime_error("add_rms: bad C");
   if (!dy || !x_new || !w || !rstd || !dx_total || !dgamma || !partial)
     throw std::runtime_error("add_rms: null backward argument");
-  arms_check_align(dy, "dy");
-  arms_check_align(x_new, "x_new");
-  arms_check_align(w, "weight");
-  arms_check_align(d_x_new, "d_x_new");
-  arms_check_align(dx_total, "dx_total");
-  arms_check_align(partial, "partials");
+  check_align(dy, 16, "add_rms", "dy");
+  check_align(x_new, 16, "add_rms", "x_new");
+  check_align(w, 16, "add_rms", "weight");
+  check_align(d_x_new, 16, "add_rms", "d_x_new");
+  check_align(dx_total, 16, "add_rms", "dx_total");
+  check_align(partial, 16, "add_rms", "partials");
   if (R <= 0) throw std::runtime_error("add_rms: empty input");
   static int cache[ARMS_MAX_NV][2][64];
   int grid = 0;
@@ -380,32 +325,14 @@ void hip_add_rms_bwd(const void* dy, const void* x_new, const void* w,
                        static_cast<const uint16_t*>(d_x_new),
                        static_cast<uint16_t*>(dx_total), partial, R);
   };
-  auto launch_nv = [&](auto with_dres, auto without, int i) {
-    if (d_x_new) launch(with_dres, cache[i][1]);
-    else launch(without, cache[i][0]);
-  };
-  switch (C / 512) {
-    case 1: launch_nv(k_add_rms_bwd<1, true>, k_add_rms_bwd<1, false>, 0);
-      break;
-    case 2: launch_nv(k_add_rms_bwd<2, true>, k_add_rms_bwd<2, false>, 1);
-      break;
-    case 3: launch_nv(k_add_rms_bwd<3, true>, k_add_rms_bwd<3, false>, 2);
-      break;
-    case 4: launch_nv(k_add_rms_bwd<4, true>, k_add_rms_bwd<4, false>, 3);
-      break;
-    case 5: launch_nv(k_add_rms_bwd<5, true>, k_add_rms_bwd<5, false>, 4);
-      break;
-    case 6: launch_nv(k_add_rms_bwd<6, true>, k_add_rms_bwd<6, false>, 5);
-      break;
-    case 7: launch_nv(k_add_rms_bwd<7, true>, k_add_rms_bwd<7, false>, 6);
-      break;
-    default: launch_nv(k_add_rms_bwd<8, true>, k_add_rms_bwd<8, false>, 7);
-      break;
-  }
-  HIP_CHECK_ARMS(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 5, 6, 7, 8>(C / 512, [&](auto NV) {
+    if (d_x_new) launch(k_add_rms_bwd<NV(), true>, cache[NV() - 1][1]);
+    else launch(k_add_rms_bwd<NV(), false>, cache[NV() - 1][0]);
+  });
+  HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_add_rms_reduce, dim3(C / 16), dim3(256), 0, s, partial,
                      grid, C, static_cast<uint16_t*>(dgamma));
-  HIP_CHECK_ARMS(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

@@ -23,18 +23,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "gelu_math.h"
 #include "hip_api.h"
 
 namespace shamd {
-
-#define HIP_CHECK_BG(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
 
 constexpr int BG_THREADS = 1024;
 // Grid cap: two resident blocks on each of MI355X's 256 CUs.  A constant,
@@ -83,8 +76,8 @@ static __device__ __forceinline__ void bg_acc(float* a, const uint4& o) {
   const uint32_t* op = &o.x;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    a[2 * k] += gl_lo(op[k]);
-    a[2 * k + 1] += gl_hi(op[k]);
+    a[2 * k] += bf16x2_lo(op[k]);
+    a[2 * k + 1] += bf16x2_hi(op[k]);
   }
 }
 
@@ -116,8 +109,8 @@ static __device__ __forceinline__ uint4 bg_gelu_bwd8(const uint4& d,
   uint32_t* op = &o.x;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    op[k] = gl_pack(gl_lo(dp[k]) * gelu_grad_f(gl_lo(up[k])),
-                    gl_hi(dp[k]) * gelu_grad_f(gl_hi(up[k])));
+    op[k] = bf16x2_pack(bf16x2_lo(dp[k]) * gelu_grad_f(bf16x2_lo(up[k])),
+                        bf16x2_hi(dp[k]) * gelu_grad_f(bf16x2_hi(up[k])));
   return o;
 }
 
@@ -204,14 +197,8 @@ __global__ __launch_bounds__(256) void k_bg_reduce(
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) t += red[i][cg];
-    out[j] = gl_bf16(t);
+    out[j] = f32_to_bf16(t);
   }
-}
-
-static void bg_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 15u)
-    throw std::runtime_error(std::string("bias_grad: ") + what +
-                             " is not 16-byte aligned");
 }
 
 static void bg_check_shape(int64_t R, int64_t N) {
@@ -239,24 +226,24 @@ static void bg_reduce(const float* partial, int G, int64_t N, void* out,
   hipLaunchKernelGGL(k_bg_reduce, dim3(static_cast<uint32_t>((N + 31) / 32)),
                      dim3(256), 0, s, partial, G, N,
                      static_cast<uint16_t*>(out));
-  HIP_CHECK_BG(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_gelu_bwd_colsum(const void* dy, const void* x, void* dx, void* db,
                          float* partial, int64_t R, int64_t C,
                          hipStream_t s) {
   bg_check_shape(R, C);
-  bg_check_align(dy, "dy");
-  bg_check_align(x, "x");
-  bg_check_align(dx, "dx");
-  bg_check_align(partial, "partial");
+  check_align(dy, 16, "bias_grad", "dy");
+  check_align(x, 16, "bias_grad", "x");
+  check_align(dx, 16, "bias_grad", "dx");
+  check_align(partial, 16, "bias_grad", "partial");
   if (!db) throw std::runtime_error("bias_grad: null db");
   const BgGeom g = bg_geom(R, C / 8, BG_GELU_ROWS);
   hipLaunchKernelGGL(k_gelu_bwd_colsum, dim3(g.gx, g.gy), dim3(BG_THREADS), 0,
                      s, static_cast<const uint4*>(dy),
                      static_cast<const uint4*>(x), static_cast<uint4*>(dx),
                      partial, R, C / 8, g.ct_shift);
-  HIP_CHECK_BG(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
   bg_reduce(partial, g.gy, C, db, s);
 }
 
@@ -264,11 +251,11 @@ void hip_pack3_colsum(const void* s0, const void* s1, const void* s2,
                       void* dst, void* db, float* partial, int64_t R,
                       int64_t C, hipStream_t s) {
   bg_check_shape(R, C);
-  bg_check_align(s0, "src0");
-  bg_check_align(s1, "src1");
-  bg_check_align(s2, "src2");
-  bg_check_align(dst, "dst");
-  bg_check_align(partial, "partial");
+  check_align(s0, 16, "bias_grad", "src0");
+  check_align(s1, 16, "bias_grad", "src1");
+  check_align(s2, 16, "bias_grad", "src2");
+  check_align(dst, 16, "bias_grad", "dst");
+  check_align(partial, 16, "bias_grad", "partial");
   if (!db) throw std::runtime_error("bias_grad: null db");
   const BgGeom g = bg_geom(R, 3 * C / 8, BG_PACK_ROWS);
   hipLaunchKernelGGL(k_pack3_colsum, dim3(g.gx, g.gy), dim3(BG_THREADS), 0, s,
@@ -276,7 +263,7 @@ void hip_pack3_colsum(const void* s0, const void* s1, const void* s2,
                      static_cast<const uint4*>(s1),
                      static_cast<const uint4*>(s2), static_cast<uint4*>(dst),
                      partial, R, C / 8, g.ct_shift);
-  HIP_CHECK_BG(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
   bg_reduce(partial, g.gy, 3 * C, db, s);
 }
 

@@ -1,8 +1,8 @@
 // Device helpers shared by the fused cross-entropy kernel files
 // (ce_kernels.hip: plain mean; ce_opts_kernels.hip: ignore_index, label
-// smoothing, z-loss), so that both run one operation chain: bf16 pair
-// packing, the head/body/tail row split, the block reductions and the
-// per-chunk max / exp-sum / gradient / store steps.
+// smoothing, z-loss), so that both run one operation chain: the
+// head/body/tail row split and the per-chunk max / exp-sum / gradient / store
+// steps.  bf16 packing and the block reductions come from device_util.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,37 +10,9 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
+
 namespace shamd {
-
-#define HIP_CHECK_CE(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ float ce_bf16_to_f32(uint16_t u) {
-  return __uint_as_float(static_cast<uint32_t>(u) << 16);
-}
-
-static __device__ __forceinline__ uint16_t ce_f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-
-static __device__ __forceinline__ float ce_pair_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float ce_pair_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint32_t ce_pair_pack(float lo, float hi) {
-  return static_cast<uint32_t>(ce_f32_to_bf16(lo)) |
-         (static_cast<uint32_t>(ce_f32_to_bf16(hi)) << 16);
-}
 
 constexpr int CE_BLOCK = 256;  // 4 waves (fwd: measured vs 512, see launcher)
 
@@ -49,33 +21,6 @@ constexpr int CE_BLOCK = 256;  // 4 waves (fwd: measured vs 512, see launcher)
 constexpr int CE_ROW_BLOCK = 1024;
 constexpr int64_t CE_ROW_CAP7 = int64_t(CE_ROW_BLOCK) * 7 * 8;    // GPT-2
 constexpr int64_t CE_ROW_CAP16 = int64_t(CE_ROW_BLOCK) * 16 * 8;  // Llama
-
-// block-wide sum (BLK/64-wave block): wave shfl tree + LDS combine
-template <int BLK>
-static __device__ __forceinline__ float block_sum(float v, float* ldsw) {
-  for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w, 64);
-  int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) ldsw[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < BLK / 64; ++i) t += ldsw[i];
-  __syncthreads();
-  return t;
-}
-
-template <int BLK>
-static __device__ __forceinline__ float block_max(float v, float* ldsw) {
-  for (int w = 32; w > 0; w >>= 1) v = fmaxf(v, __shfl_down(v, w, 64));
-  int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) ldsw[wave] = v;
-  __syncthreads();
-  float t = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < BLK / 64; ++i) t = fmaxf(t, ldsw[i]);
-  __syncthreads();
-  return t;
-}
 
 // Rows are only 2-byte aligned when V is odd (GPT-2: V = 50257), so each
 // row is processed as [head: up to 7 elems | body: 16-byte-aligned chunks of
@@ -104,18 +49,18 @@ static __device__ __forceinline__ int64_t ce_edge_index(const CeRow& g, int e,
 }
 
 static __device__ __forceinline__ float ce_max8(const uint4& u) {
-  float a = fmaxf(fmaxf(ce_pair_lo(u.x), ce_pair_hi(u.x)),
-                  fmaxf(ce_pair_lo(u.y), ce_pair_hi(u.y)));
-  float b = fmaxf(fmaxf(ce_pair_lo(u.z), ce_pair_hi(u.z)),
-                  fmaxf(ce_pair_lo(u.w), ce_pair_hi(u.w)));
+  float a = fmaxf(fmaxf(bf16x2_lo(u.x), bf16x2_hi(u.x)),
+                  fmaxf(bf16x2_lo(u.y), bf16x2_hi(u.y)));
+  float b = fmaxf(fmaxf(bf16x2_lo(u.z), bf16x2_hi(u.z)),
+                  fmaxf(bf16x2_lo(u.w), bf16x2_hi(u.w)));
   return fmaxf(a, b);
 }
 
 static __device__ __forceinline__ float ce_expsum8(const uint4& u, float m) {
-  float a = __expf(ce_pair_lo(u.x) - m) + __expf(ce_pair_hi(u.x) - m);
-  float b = __expf(ce_pair_lo(u.y) - m) + __expf(ce_pair_hi(u.y) - m);
-  float c = __expf(ce_pair_lo(u.z) - m) + __expf(ce_pair_hi(u.z) - m);
-  float d = __expf(ce_pair_lo(u.w) - m) + __expf(ce_pair_hi(u.w) - m);
+  float a = __expf(bf16x2_lo(u.x) - m) + __expf(bf16x2_hi(u.x) - m);
+  float b = __expf(bf16x2_lo(u.y) - m) + __expf(bf16x2_hi(u.y) - m);
+  float c = __expf(bf16x2_lo(u.z) - m) + __expf(bf16x2_hi(u.z) - m);
+  float d = __expf(bf16x2_lo(u.w) - m) + __expf(bf16x2_hi(u.w) - m);
   return (a + b) + (c + d);
 }
 
@@ -127,8 +72,8 @@ static __device__ __forceinline__ float ce_grad1(float x, float lse,
 // gradient of one pair; d = (target index) - (index of the pair's low elem)
 static __device__ __forceinline__ uint32_t ce_grad_pair(uint32_t p, float lse,
                                                         float gscale, int d) {
-  return ce_pair_pack(ce_grad1(ce_pair_lo(p), lse, gscale, d == 0),
-                      ce_grad1(ce_pair_hi(p), lse, gscale, d == 1));
+  return bf16x2_pack(ce_grad1(bf16x2_lo(p), lse, gscale, d == 0),
+                     ce_grad1(bf16x2_hi(p), lse, gscale, d == 1));
 }
 
 // gradient of one body chunk; d = (target index) - (index of its first elem)

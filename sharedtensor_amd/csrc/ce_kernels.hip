@@ -43,7 +43,7 @@ __global__ void k_ce_fwd(const uint16_t* __restrict__ logits,
   const int e = threadIdx.x;
   const bool edge = e < g.head + g.tail;
   const float xe =
-      edge ? ce_bf16_to_f32(xr[ce_edge_index(g, e, V)]) : -INFINITY;
+      edge ? bf16_to_f32(xr[ce_edge_index(g, e, V)]) : -INFINITY;
 
   float m = xe;
   for (int64_t c = threadIdx.x; c < g.nbody; c += BLK) m = fmaxf(m, ce_max8(xb[c]));
@@ -54,7 +54,7 @@ __global__ void k_ce_fwd(const uint16_t* __restrict__ logits,
   float tot = block_sum<BLK>(s, lds4);
   if (threadIdx.x == 0) {
     float lse = __logf(tot) + m;
-    float xt = ce_bf16_to_f32(xr[targets[r]]);
+    float xt = bf16_to_f32(xr[targets[r]]);
     loss[r] = lse - xt;
     row_m[r] = m;
     row_lse[r] = lse;
@@ -104,7 +104,7 @@ k_ce_fwd_grad(const uint16_t* __restrict__ logits,
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) v[k] = make_uint4(0, 0, 0, 0);
   }
-  const float xe = edge ? ce_bf16_to_f32(xr[ei]) : -INFINITY;
+  const float xe = edge ? bf16_to_f32(xr[ei]) : -INFINITY;
   const int tgt = targets[r];
 
   float m = xe;
@@ -120,7 +120,7 @@ k_ce_fwd_grad(const uint16_t* __restrict__ logits,
   const float tot = block_sum<BLK>(s, ldsw);
   const float lse = __logf(tot) + m;
   if (threadIdx.x == 0) {
-    loss[r] = lse - ce_bf16_to_f32(xr[tgt]);
+    loss[r] = lse - bf16_to_f32(xr[tgt]);
     row_lse[r] = lse;
   }
 
@@ -133,7 +133,7 @@ k_ce_fwd_grad(const uint16_t* __restrict__ logits,
       ce_store8(db + 8 * c, ce_grad8(v[k], lse, inv_r, tgt - g.head - 8 * c),
                 aligned);
   }
-  if (edge) dr[ei] = ce_f32_to_bf16(ce_grad1(xe, lse, inv_r, ei == tgt));
+  if (edge) dr[ei] = f32_to_bf16(ce_grad1(xe, lse, inv_r, ei == tgt));
 }
 
 // Grid-stride over rows.  SKIP_IF_UNIT: the buffer already holds the g == 1
@@ -182,8 +182,8 @@ __global__ void k_ce_bwd(const uint16_t* __restrict__ logits,
     const int e = threadIdx.x;
     if (e < g.head + g.tail) {
       int64_t ei = ce_edge_index(g, e, V);
-      dr[ei] = ce_f32_to_bf16(
-          ce_grad1(ce_bf16_to_f32(xr[ei]), lse, gscale, ei == tgt));
+      dr[ei] = f32_to_bf16(
+          ce_grad1(bf16_to_f32(xr[ei]), lse, gscale, ei == tgt));
     }
   }
 }
@@ -210,7 +210,7 @@ void hip_ce_fwd(const void* logits, const int32_t* targets, float* loss,
                        dim3(CE_BLOCK), 0, s,
                        static_cast<const uint16_t*>(logits), targets, loss,
                        row_m, row_lse, V);
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 // register capacity of the k_ce_fwd_grad instantiations: ce_common.h
@@ -231,7 +231,7 @@ void hip_ce_fwd_grad(const void* logits, const int32_t* targets, float* loss,
                        dim3(static_cast<uint32_t>(R)), dim3(CE_ROW_BLOCK), 0,
                        s, static_cast<const uint16_t*>(logits), targets, loss,
                        row_lse, static_cast<uint16_t*>(dlogits), inv_r, V);
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 template <int BLK>
@@ -269,7 +269,7 @@ void hip_ce_bwd(const void* logits, const int32_t* targets,
   else
     launch_ce_bwd<CE_BLOCK>(logits, targets, row_lse, dlogits, gscale_dev,
                             inv_r, R, V, skip_if_unit, s);
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

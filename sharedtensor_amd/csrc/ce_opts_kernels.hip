@@ -96,8 +96,8 @@ struct CeGrad {
     }
   }
   __device__ __forceinline__ uint32_t pair(uint32_t p, float lse, int d) const {
-    return ce_pair_pack(one(ce_pair_lo(p), lse, d == 0),
-                        one(ce_pair_hi(p), lse, d == 1));
+    return bf16x2_pack(one(bf16x2_lo(p), lse, d == 0),
+                       one(bf16x2_hi(p), lse, d == 1));
   }
   // d = (target index) - (index of the chunk's first elem)
   __device__ __forceinline__ uint4 chunk(const uint4& u, float lse, int d) const {
@@ -233,7 +233,7 @@ k_ce_opts_fwd_grad(const uint16_t* __restrict__ logits,
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) v[k] = make_uint4(0, 0, 0, 0);
   }
-  const float xe = edge ? ce_bf16_to_f32(xr[ei]) : -INFINITY;
+  const float xe = edge ? bf16_to_f32(xr[ei]) : -INFINITY;
   const float inv_count = state->inv_count;
 
   float m = xe;
@@ -266,7 +266,7 @@ k_ce_opts_fwd_grad(const uint16_t* __restrict__ logits,
   // waits until the row's registers are free (after the stores)
   if constexpr (!EXTRA) {
     if (threadIdx.x == 0) {
-      loss[r] = ce_row_loss<EXTRA>(lse, ce_bf16_to_f32(xr[tgt]), sx, V, eps, z);
+      loss[r] = ce_row_loss<EXTRA>(lse, bf16_to_f32(xr[tgt]), sx, V, eps, z);
       row_lse[r] = lse;
     }
   }
@@ -280,10 +280,10 @@ k_ce_opts_fwd_grad(const uint16_t* __restrict__ logits,
     if (c < nbody)
       ce_store8(db + 8 * c, cg.chunk(v[k], lse, tgt - g.head - 8 * c), aligned);
   }
-  if (edge) dr[ei] = ce_f32_to_bf16(cg.one(xe, lse, ei == tgt));
+  if (edge) dr[ei] = f32_to_bf16(cg.one(xe, lse, ei == tgt));
   if constexpr (EXTRA) {
     if (threadIdx.x == 0) {
-      loss[r] = ce_row_loss<EXTRA>(lse, ce_bf16_to_f32(xr[tgt]), sx, V, eps, z);
+      loss[r] = ce_row_loss<EXTRA>(lse, bf16_to_f32(xr[tgt]), sx, V, eps, z);
       row_lse[r] = lse;
     }
   }
@@ -313,7 +313,7 @@ __global__ void k_ce_opts_fwd(const uint16_t* __restrict__ logits,
   const int e = threadIdx.x;
   const bool edge = e < g.head + g.tail;
   const float xe =
-      edge ? ce_bf16_to_f32(xr[ce_edge_index(g, e, V)]) : -INFINITY;
+      edge ? bf16_to_f32(xr[ce_edge_index(g, e, V)]) : -INFINITY;
 
   float m = xe;
   float a = edge ? xe : 0.f;
@@ -331,7 +331,7 @@ __global__ void k_ce_opts_fwd(const uint16_t* __restrict__ logits,
   float tot = block_sum<BLK>(s, lds4);
   if (threadIdx.x == 0) {
     float lse = __logf(tot) + m;
-    loss[r] = ce_row_loss<EXTRA>(lse, ce_bf16_to_f32(xr[tgt]), sx, V, eps, z);
+    loss[r] = ce_row_loss<EXTRA>(lse, bf16_to_f32(xr[tgt]), sx, V, eps, z);
     row_lse[r] = lse;
   }
 }
@@ -387,7 +387,7 @@ __global__ void k_ce_opts_bwd(const uint16_t* __restrict__ logits,
     const int e = threadIdx.x;
     if (e < g.head + g.tail) {
       int64_t ei = ce_edge_index(g, e, V);
-      dr[ei] = ce_f32_to_bf16(cg.one(ce_bf16_to_f32(xr[ei]), lse, ei == tgt));
+      dr[ei] = f32_to_bf16(cg.one(bf16_to_f32(xr[ei]), lse, ei == tgt));
     }
   }
 }
@@ -411,7 +411,7 @@ void hip_ce_opts_scan(const int32_t* targets, int64_t R, int64_t V,
   hipLaunchKernelGGL(k_ce_opts_scan<CE_ROW_BLOCK>, dim3(1), dim3(CE_ROW_BLOCK),
                      0, s, targets, R, V, o.ignore_index,
                      o.has_ignore ? 1 : 0, state);
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 template <int NCHUNK, bool EXTRA>
@@ -450,7 +450,7 @@ void hip_ce_opts_fwd_grad(const void* logits, const int32_t* targets,
       launch_ce_opts_fwd_grad<16, false>(logits, targets, loss, row_lse,
                                          dlogits, state, o, R, V, s);
   }
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_ce_opts_fwd(const void* logits, const int32_t* targets, float* loss,
@@ -468,7 +468,7 @@ void hip_ce_opts_fwd(const void* logits, const int32_t* targets, float* loss,
                        0, s, static_cast<const uint16_t*>(logits), targets,
                        loss, row_lse, V, o.ignore_index, o.has_ignore ? 1 : 0,
                        o.eps, o.z);
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 template <bool SKIP, bool EXTRA>
@@ -510,7 +510,7 @@ void hip_ce_opts_bwd(const void* logits, const int32_t* targets,
       launch_ce_opts_bwd<false, false>(logits, targets, row_lse, dlogits,
                                        gscale_dev, state, o, R, V, s);
   }
-  HIP_CHECK_CE(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

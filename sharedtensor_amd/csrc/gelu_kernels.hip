@@ -7,18 +7,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "gelu_math.h"
 #include "hip_api.h"
 
 namespace shamd {
-
-#define HIP_CHECK_GL(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
 
 // uint4 (8 bf16) per iteration — the pair-only variant measured SLOWER
 // than torch's 8-wide elementwise kernels in round 1; round 2's SwiGLU
@@ -33,7 +26,7 @@ __global__ void k_gelu_fwd(const uint4* __restrict__ x,
     uint32_t* op = &o.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      op[k] = gl_pack(gelu_f(gl_lo(up[k])), gelu_f(gl_hi(up[k])));
+      op[k] = bf16x2_pack(gelu_f(bf16x2_lo(up[k])), gelu_f(bf16x2_hi(up[k])));
     y[i] = o;
   }
 }
@@ -50,19 +43,10 @@ __global__ void k_gelu_bwd(const uint4* __restrict__ dy,
     uint32_t* op = &o.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      op[k] = gl_pack(gl_lo(dp[k]) * gelu_grad_f(gl_lo(up[k])),
-                      gl_hi(dp[k]) * gelu_grad_f(gl_hi(up[k])));
+      op[k] = bf16x2_pack(bf16x2_lo(dp[k]) * gelu_grad_f(bf16x2_lo(up[k])),
+                          bf16x2_hi(dp[k]) * gelu_grad_f(bf16x2_hi(up[k])));
     dx[i] = o;
   }
-}
-
-// The kernels load and store uint4.  contiguous() keeps an offset view of a
-// larger buffer as it is, so the pointers are checked here; the Python
-// wrapper clones a tensor that fails this.
-static void gelu_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 15u)
-    throw std::runtime_error(std::string("gelu: ") + what +
-                             " is not 16-byte aligned");
 }
 
 static inline int gelu_grid(int64_t npairs) {
@@ -74,27 +58,27 @@ void hip_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s) {
   // the wrapper arranges n % 8 == 0 and 16-byte alignment; both are
   // checked here because nothing else guarantees them
   if (n % 8) throw std::runtime_error("gelu: n must be a multiple of 8");
-  gelu_check_align(x, "x");
-  gelu_check_align(y, "y");
+  check_align(x, 16, "gelu", "x");
+  check_align(y, 16, "gelu", "y");
   if (n <= 0) return;
   hipLaunchKernelGGL(k_gelu_fwd, dim3(gelu_grid(n / 8)), dim3(256), 0, s,
                      static_cast<const uint4*>(x),
                      static_cast<uint4*>(y), n / 8);
-  HIP_CHECK_GL(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n,
                   hipStream_t s) {
   if (n % 8) throw std::runtime_error("gelu: n must be a multiple of 8");
-  gelu_check_align(dy, "dy");
-  gelu_check_align(x, "x");
-  gelu_check_align(dx, "dx");
+  check_align(dy, 16, "gelu", "dy");
+  check_align(x, 16, "gelu", "x");
+  check_align(dx, 16, "gelu", "dx");
   if (n <= 0) return;
   hipLaunchKernelGGL(k_gelu_bwd, dim3(gelu_grid(n / 8)), dim3(256), 0, s,
                      static_cast<const uint4*>(dy),
                      static_cast<const uint4*>(x),
                      static_cast<uint4*>(dx), n / 8);
-  HIP_CHECK_GL(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

@@ -1,4 +1,4 @@
-// Device-side bf16 packing and tanh-GELU math shared by gelu_kernels.hip and
+// Device-side tanh-GELU math shared by gelu_kernels.hip and
 // bias_grad_kernels.hip, so both evaluate the very same expressions.
 #pragma once
 
@@ -6,24 +6,9 @@
 
 #include <cstdint>
 
-namespace shamd {
+#include "device_util.h"
 
-static __device__ __forceinline__ float gl_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float gl_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint16_t gl_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-static __device__ __forceinline__ uint32_t gl_pack(float lo, float hi) {
-  return static_cast<uint32_t>(gl_bf16(lo)) |
-         (static_cast<uint32_t>(gl_bf16(hi)) << 16);
-}
+namespace shamd {
 
 // gelu(x) = 0.5 x (1 + tanh(k (x + 0.044715 x^3))), k = sqrt(2/pi)
 constexpr float GK = 0.7978845608028654f;

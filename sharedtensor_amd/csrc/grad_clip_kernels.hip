@@ -15,17 +15,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"
 
 namespace shamd {
-
-#define HIP_CHECK_GC(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
 
 constexpr int GC_BLOCK = 256;
 constexpr int GC_WAVES = GC_BLOCK / 64;
@@ -38,7 +31,7 @@ __device__ __forceinline__ double gc_elem_sq(const float* g, int64_t i) {
   return gc_sq(g[i]);
 }
 __device__ __forceinline__ double gc_elem_sq(const uint16_t* g, int64_t i) {
-  return gc_sq(__uint_as_float(static_cast<uint32_t>(g[i]) << 16));
+  return gc_sq(bf16_to_f32(g[i]));
 }
 
 // acc[0..3] += squares of the 16 bytes in q
@@ -52,8 +45,8 @@ __device__ __forceinline__ void gc_vec_sq(const uint16_t*, uint4 q, double* acc)
   const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    acc[k] += gc_sq(__uint_as_float(w[k] << 16));
-    acc[k] += gc_sq(__uint_as_float(w[k] & 0xFFFF0000u));
+    acc[k] += gc_sq(bf16x2_lo(w[k]));
+    acc[k] += gc_sq(bf16x2_hi(w[k]));
   }
 }
 
@@ -158,7 +151,7 @@ void hip_grad_clip_coef(const void* grad, bool grad_bf16, int64_t n,
                        static_cast<const float*>(grad), n, scratch);
   hipLaunchKernelGGL(k_grad_clip_finalize, dim3(1), dim3(GC_BLOCK), 0, s,
                      scratch, g, max_norm, state);
-  HIP_CHECK_GC(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

@@ -32,19 +32,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"
 #include "optim_step.h"
 
 namespace shamd {
-
-#define HIP_CHECK(expr)                                                    \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e) + " at " __FILE__ ":" + \
-                               std::to_string(__LINE__));                  \
-  } while (0)
 
 constexpr int BLOCK = 256;
 
@@ -56,8 +48,8 @@ static inline int grid_for(int64_t n) {
 
 // ---------------------------------------------------------------- helpers
 
-// bf16 conversions, add/mul_uncontracted and the residual-delta storage
-// policies (DeltaF32, DeltaBF16) live in optim_step.h.
+// bf16 conversions live in device_util.h; add/mul_uncontracted and the
+// residual-delta storage policies (DeltaF32, DeltaBF16) in optim_step.h.
 
 // Binary search: largest t with poffs[t] <= j.  T is small (1..few hundred)
 // and the array is L2-hot; for T==1 the caller's fast path skips this.

@@ -21,63 +21,12 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"  // declaration parity check
 
 namespace shamd {
 
-#define HIP_CHECK_LN(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ float ln_bf16_to_f32(uint16_t u) {
-  return __uint_as_float(static_cast<uint32_t>(u) << 16);
-}
-
-static __device__ __forceinline__ uint16_t ln_f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-
-static __device__ __forceinline__ float bf16pair_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float bf16pair_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint32_t bf16pair_pack(float lo, float hi) {
-  return static_cast<uint32_t>(ln_f32_to_bf16(lo)) |
-         (static_cast<uint32_t>(ln_f32_to_bf16(hi)) << 16);
-}
-
 constexpr int LN_BLOCK = 256;  // 4 waves
-
-// The fwd and dx kernels load and store bf16 pairs as uint32.  contiguous()
-// keeps an offset view of a larger buffer as it is, so the callers' pointers
-// are checked here, before any launch.  (The dw/db and colsum kernels load
-// scalars and take any bf16 pointer.)
-static void ln_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 3u)
-    throw std::runtime_error(std::string("ln/rms: ") + what +
-                             " is not 4-byte aligned");
-}
-
-// Block-wide sum of one value per thread (4-wave block): wave shfl tree +
-// LDS combine.  Returns the total to every thread.
-static __device__ __forceinline__ float block_sum(float v, float* lds4) {
-  for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w, 64);
-  int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds4[wave] = v;
-  __syncthreads();
-  float t = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-  __syncthreads();
-  return t;
-}
 
 // Per-thread register cache for a row's owned elements.  CPT (elements per
 // thread) is a template parameter so the caches index statically and stay
@@ -105,14 +54,14 @@ __global__ void k_ln_fwd(const uint16_t* __restrict__ x,
     float a = 0.f, bb = 0.f;
     if (c < C2) {
       uint32_t pk = xr[c];
-      a = bf16pair_lo(pk);
-      bb = bf16pair_hi(pk);
+      a = bf16x2_lo(pk);
+      bb = bf16x2_hi(pk);
     }
     x0[k] = a;
     x1[k] = bb;
     s += a + bb;
   }
-  float m = block_sum(s, lds4) / C;
+  float m = block_sum<LN_BLOCK>(s, lds4) / C;
   // two-pass variance from the cached row: sum((x - m)^2) does not cancel
   // the way sum(x^2)/C - m^2 does when |mean| >> std.  Columns past the row
   // hold 0 in the cache and must add 0 here, not m^2.
@@ -125,7 +74,7 @@ __global__ void k_ln_fwd(const uint16_t* __restrict__ x,
       ss += d0 * d0 + d1 * d1;
     }
   }
-  float rs = rsqrtf(block_sum(ss, lds4) / C + eps);
+  float rs = rsqrtf(block_sum<LN_BLOCK>(ss, lds4) / C + eps);
   if (threadIdx.x == 0) {
     mean[r] = m;
     rstd[r] = rs;
@@ -135,14 +84,14 @@ __global__ void k_ln_fwd(const uint16_t* __restrict__ x,
     int c = threadIdx.x + k * LN_BLOCK;
     if (c < C2) {
       uint32_t wk = wp[c];
-      float o0 = (x0[k] - m) * rs * bf16pair_lo(wk);
-      float o1 = (x1[k] - m) * rs * bf16pair_hi(wk);
+      float o0 = (x0[k] - m) * rs * bf16x2_lo(wk);
+      float o1 = (x1[k] - m) * rs * bf16x2_hi(wk);
       if (bp) {
         uint32_t bk = bp[c];
-        o0 += bf16pair_lo(bk);
-        o1 += bf16pair_hi(bk);
+        o0 += bf16x2_lo(bk);
+        o1 += bf16x2_hi(bk);
       }
-      yr[c] = bf16pair_pack(o0, o1);
+      yr[c] = bf16x2_pack(o0, o1);
     }
   }
 }
@@ -170,10 +119,10 @@ __global__ void k_ln_bwd_dx(const uint16_t* __restrict__ dy,
     float u0 = 0.f, u1 = 0.f, v0 = 0.f, v1 = 0.f;
     if (c < C2) {
       uint32_t dk = dyr[c], wk = wp[c], xk = xr[c];
-      u0 = bf16pair_lo(dk) * bf16pair_lo(wk);
-      u1 = bf16pair_hi(dk) * bf16pair_hi(wk);
-      v0 = (bf16pair_lo(xk) - m) * rs;
-      v1 = (bf16pair_hi(xk) - m) * rs;
+      u0 = bf16x2_lo(dk) * bf16x2_lo(wk);
+      u1 = bf16x2_hi(dk) * bf16x2_hi(wk);
+      v0 = (bf16x2_lo(xk) - m) * rs;
+      v1 = (bf16x2_hi(xk) - m) * rs;
     }
     a0[k] = u0;
     a1[k] = u1;
@@ -182,14 +131,14 @@ __global__ void k_ln_bwd_dx(const uint16_t* __restrict__ dy,
     s1 += u0 + u1;
     s2 += u0 * v0 + u1 * v1;
   }
-  float t1 = block_sum(s1, lds4) / C;
-  float t2 = block_sum(s2, lds4) / C;
+  float t1 = block_sum<LN_BLOCK>(s1, lds4) / C;
+  float t2 = block_sum<LN_BLOCK>(s2, lds4) / C;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     int c = threadIdx.x + k * LN_BLOCK;
     if (c < C2)
-      dxr[c] = bf16pair_pack((a0[k] - t1 - h0[k] * t2) * rs,
-                             (a1[k] - t1 - h1[k] * t2) * rs);
+      dxr[c] = bf16x2_pack((a0[k] - t1 - h0[k] * t2) * rs,
+                           (a1[k] - t1 - h1[k] * t2) * rs);
   }
 }
 
@@ -216,8 +165,8 @@ __global__ void k_ln_bwd_dwdb(const uint16_t* __restrict__ dy,
     for (int k = 0; k < CPT; ++k) {
       int c = threadIdx.x + k * LN_BLOCK;
       if (c < C) {
-        float g = ln_bf16_to_f32(dyr[c]);
-        float xh = (ln_bf16_to_f32(xr[c]) - m) * rs;
+        float g = bf16_to_f32(dyr[c]);
+        float xh = (bf16_to_f32(xr[c]) - m) * rs;
         accg[k] += g * xh;
         accb[k] += g;
       }
@@ -260,14 +209,14 @@ __global__ void k_rms_fwd(const uint16_t* __restrict__ x,
     float a = 0.f, b = 0.f;
     if (c < C2) {
       uint32_t pk = xr[c];
-      a = bf16pair_lo(pk);
-      b = bf16pair_hi(pk);
+      a = bf16x2_lo(pk);
+      b = bf16x2_hi(pk);
     }
     x0[k] = a;
     x1[k] = b;
     ss += a * a + b * b;
   }
-  float tot2 = block_sum(ss, lds4);
+  float tot2 = block_sum<LN_BLOCK>(ss, lds4);
   float rs = rsqrtf(tot2 / C + eps);
   if (threadIdx.x == 0) rstd[r] = rs;
 #pragma unroll
@@ -275,8 +224,8 @@ __global__ void k_rms_fwd(const uint16_t* __restrict__ x,
     int c = threadIdx.x + k * LN_BLOCK;
     if (c < C2) {
       uint32_t wk = wp[c];
-      yr[c] = bf16pair_pack(x0[k] * rs * bf16pair_lo(wk),
-                            x1[k] * rs * bf16pair_hi(wk));
+      yr[c] = bf16x2_pack(x0[k] * rs * bf16x2_lo(wk),
+                          x1[k] * rs * bf16x2_hi(wk));
     }
   }
 }
@@ -303,10 +252,10 @@ __global__ void k_rms_bwd_dx(const uint16_t* __restrict__ dy,
     float u0 = 0.f, u1 = 0.f, a = 0.f, b = 0.f;
     if (c < C2) {
       uint32_t dk = dyr[c], wk = wp[c], xk = xr[c];
-      u0 = bf16pair_lo(dk) * bf16pair_lo(wk);
-      u1 = bf16pair_hi(dk) * bf16pair_hi(wk);
-      a = bf16pair_lo(xk);
-      b = bf16pair_hi(xk);
+      u0 = bf16x2_lo(dk) * bf16x2_lo(wk);
+      u1 = bf16x2_hi(dk) * bf16x2_hi(wk);
+      a = bf16x2_lo(xk);
+      b = bf16x2_hi(xk);
     }
     g0[k] = u0;
     g1[k] = u1;
@@ -314,13 +263,13 @@ __global__ void k_rms_bwd_dx(const uint16_t* __restrict__ dy,
     v1[k] = b;
     s += u0 * a + u1 * b;
   }
-  float t = block_sum(s, lds4) / C * rs * rs;
+  float t = block_sum<LN_BLOCK>(s, lds4) / C * rs * rs;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     int c = threadIdx.x + k * LN_BLOCK;
     if (c < C2)
-      dxr[c] = bf16pair_pack((g0[k] - v0[k] * t) * rs,
-                             (g1[k] - v1[k] * t) * rs);
+      dxr[c] = bf16x2_pack((g0[k] - v0[k] * t) * rs,
+                           (g1[k] - v1[k] * t) * rs);
   }
 }
 
@@ -340,7 +289,7 @@ __global__ void k_rms_bwd_dw(const uint16_t* __restrict__ dy,
     for (int k = 0; k < CPT; ++k) {
       int c = threadIdx.x + k * LN_BLOCK;
       if (c < C)
-        accg[k] += ln_bf16_to_f32(dyr[c]) * ln_bf16_to_f32(xr[c]) * rs;
+        accg[k] += bf16_to_f32(dyr[c]) * bf16_to_f32(xr[c]) * rs;
     }
   }
 #pragma unroll
@@ -353,9 +302,11 @@ __global__ void k_rms_bwd_dw(const uint16_t* __restrict__ dy,
 void hip_rms_fwd(const void* x, const void* w, void* y, float* rstd,
                  int64_t R, int C, float eps, hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("rms: bad C");
-  ln_check_align(x, "x");
-  ln_check_align(w, "weight");
-  ln_check_align(y, "y");
+  // the fwd and dx kernels load and store bf16 pairs as uint32 (the dw/db and
+  // colsum kernels load scalars and take any bf16 pointer)
+  check_align(x, 4, "ln/rms", "x");
+  check_align(w, 4, "ln/rms", "weight");
+  check_align(y, 4, "ln/rms", "y");
   if (R <= 0) return;  // a grid of 0 blocks is an invalid configuration
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch = [&](auto kern) {
@@ -364,22 +315,18 @@ void hip_rms_fwd(const void* x, const void* w, void* y, float* rstd,
                        static_cast<const uint16_t*>(w),
                        static_cast<uint16_t*>(y), rstd, C, eps);
   };
-  if (cpt <= 1) launch(k_rms_fwd<1>);
-  else if (cpt <= 2) launch(k_rms_fwd<2>);
-  else if (cpt <= 3) launch(k_rms_fwd<3>);
-  else if (cpt <= 4) launch(k_rms_fwd<4>);
-  else launch(k_rms_fwd<8>);  // C <= LN_MAXC: cpt <= 8
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8>(cpt, [&](auto K) { launch(k_rms_fwd<K()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_rms_bwd(const void* dy, const void* x, const void* w,
                  const float* rstd, void* dx, float* dgamma, int64_t R, int C,
                  hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("rms: bad C");
-  ln_check_align(dy, "dy");
-  ln_check_align(x, "x");
-  ln_check_align(w, "weight");
-  ln_check_align(dx, "dx");
+  check_align(dy, 4, "ln/rms", "dy");
+  check_align(x, 4, "ln/rms", "x");
+  check_align(w, 4, "ln/rms", "weight");
+  check_align(dx, 4, "ln/rms", "dx");
   if (R <= 0) return;  // dgamma stays as the caller zeroed it
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch_dx = [&](auto kern) {
@@ -389,12 +336,9 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
                        static_cast<const uint16_t*>(w), rstd,
                        static_cast<uint16_t*>(dx), C);
   };
-  if (cpt <= 1) launch_dx(k_rms_bwd_dx<1>);
-  else if (cpt <= 2) launch_dx(k_rms_bwd_dx<2>);
-  else if (cpt <= 3) launch_dx(k_rms_bwd_dx<3>);
-  else if (cpt <= 4) launch_dx(k_rms_bwd_dx<4>);
-  else launch_dx(k_rms_bwd_dx<8>);  // C <= LN_MAXC: cpt <= 8
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8>(
+      cpt, [&](auto K) { launch_dx(k_rms_bwd_dx<K()>); });
+  HIP_CHECK(hipGetLastError());
   int g = R < 2048 ? static_cast<int>(R) : 2048;  // 8 blocks/CU (see LN note)
   int ecpt = (C + LN_BLOCK - 1) / LN_BLOCK;
   auto launch_dw = [&](auto kern) {
@@ -402,13 +346,9 @@ void hip_rms_bwd(const void* dy, const void* x, const void* w,
                        static_cast<const uint16_t*>(dy),
                        static_cast<const uint16_t*>(x), rstd, dgamma, R, C);
   };
-  if (ecpt <= 1) launch_dw(k_rms_bwd_dw<1>);
-  else if (ecpt <= 2) launch_dw(k_rms_bwd_dw<2>);
-  else if (ecpt <= 3) launch_dw(k_rms_bwd_dw<3>);
-  else if (ecpt <= 4) launch_dw(k_rms_bwd_dw<4>);
-  else if (ecpt <= 8) launch_dw(k_rms_bwd_dw<8>);
-  else launch_dw(k_rms_bwd_dw<16>);
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8, 16>(
+      ecpt, [&](auto K) { launch_dw(k_rms_bwd_dw<K()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 // Column sum of a (R, C) bf16 matrix into fp32 out[C] — the bias-gradient
@@ -427,7 +367,7 @@ __global__ void k_colsum_bf16(const uint16_t* __restrict__ x,
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
       int c = threadIdx.x + k * LN_BLOCK;
-      if (c < C) acc[k] += ln_bf16_to_f32(xr[c]);
+      if (c < C) acc[k] += bf16_to_f32(xr[c]);
     }
   }
 #pragma unroll
@@ -447,23 +387,19 @@ void hip_colsum_bf16(const void* x, float* out, int64_t R, int C,
     hipLaunchKernelGGL(kern, dim3(g), dim3(LN_BLOCK), 0, s,
                        static_cast<const uint16_t*>(x), out, R, C);
   };
-  if (ecpt <= 1) launch(k_colsum_bf16<1>);
-  else if (ecpt <= 2) launch(k_colsum_bf16<2>);
-  else if (ecpt <= 3) launch(k_colsum_bf16<3>);
-  else if (ecpt <= 4) launch(k_colsum_bf16<4>);
-  else if (ecpt <= 8) launch(k_colsum_bf16<8>);
-  else launch(k_colsum_bf16<16>);
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8, 16>(
+      ecpt, [&](auto K) { launch(k_colsum_bf16<K()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_ln_fwd(const void* x, const void* w, const void* b, void* y,
                 float* mean, float* rstd, int64_t R, int C, float eps,
                 hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("ln: bad C");
-  ln_check_align(x, "x");
-  ln_check_align(w, "weight");
-  ln_check_align(b, "bias");
-  ln_check_align(y, "y");
+  check_align(x, 4, "ln/rms", "x");
+  check_align(w, 4, "ln/rms", "weight");
+  check_align(b, 4, "ln/rms", "bias");
+  check_align(y, 4, "ln/rms", "y");
   if (R <= 0) return;
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch = [&](auto kern) {
@@ -473,22 +409,18 @@ void hip_ln_fwd(const void* x, const void* w, const void* b, void* y,
                        static_cast<const uint16_t*>(b),
                        static_cast<uint16_t*>(y), mean, rstd, C, eps);
   };
-  if (cpt <= 1) launch(k_ln_fwd<1>);
-  else if (cpt <= 2) launch(k_ln_fwd<2>);
-  else if (cpt <= 3) launch(k_ln_fwd<3>);
-  else if (cpt <= 4) launch(k_ln_fwd<4>);
-  else launch(k_ln_fwd<8>);  // C <= LN_MAXC: cpt <= 8
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8>(cpt, [&](auto K) { launch(k_ln_fwd<K()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_ln_bwd(const void* dy, const void* x, const void* w,
                 const float* mean, const float* rstd, void* dx, float* dgamma,
                 float* dbeta, int64_t R, int C, hipStream_t s) {
   if (C > LN_MAXC || (C & 1)) throw std::runtime_error("ln: bad C");
-  ln_check_align(dy, "dy");
-  ln_check_align(x, "x");
-  ln_check_align(w, "weight");
-  ln_check_align(dx, "dx");
+  check_align(dy, 4, "ln/rms", "dy");
+  check_align(x, 4, "ln/rms", "x");
+  check_align(w, 4, "ln/rms", "weight");
+  check_align(dx, 4, "ln/rms", "dx");
   if (R <= 0) return;  // dgamma/dbeta stay as the caller zeroed them
   int cpt = (C / 2 + LN_BLOCK - 1) / LN_BLOCK;
   auto launch_dx = [&](auto kern) {
@@ -498,12 +430,9 @@ void hip_ln_bwd(const void* dy, const void* x, const void* w,
                        static_cast<const uint16_t*>(w), mean, rstd,
                        static_cast<uint16_t*>(dx), C);
   };
-  if (cpt <= 1) launch_dx(k_ln_bwd_dx<1>);
-  else if (cpt <= 2) launch_dx(k_ln_bwd_dx<2>);
-  else if (cpt <= 3) launch_dx(k_ln_bwd_dx<3>);
-  else if (cpt <= 4) launch_dx(k_ln_bwd_dx<4>);
-  else launch_dx(k_ln_bwd_dx<8>);  // C <= LN_MAXC: cpt <= 8
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8>(
+      cpt, [&](auto K) { launch_dx(k_ln_bwd_dx<K()>); });
+  HIP_CHECK(hipGetLastError());
   // 2048 blocks = 8 per CU: enough waves to hide the strided bf16 loads
   // (256 blocks measured 0.67 TB/s — latency-bound at 1 block/CU); the
   // per-column atomic count stays trivial (2048 per column).
@@ -515,13 +444,9 @@ void hip_ln_bwd(const void* dy, const void* x, const void* w,
                        static_cast<const uint16_t*>(x), mean, rstd, dgamma,
                        dbeta, R, C);
   };
-  if (ecpt <= 1) launch_dw(k_ln_bwd_dwdb<1>);
-  else if (ecpt <= 2) launch_dw(k_ln_bwd_dwdb<2>);
-  else if (ecpt <= 3) launch_dw(k_ln_bwd_dwdb<3>);
-  else if (ecpt <= 4) launch_dw(k_ln_bwd_dwdb<4>);
-  else if (ecpt <= 8) launch_dw(k_ln_bwd_dwdb<8>);
-  else launch_dw(k_ln_bwd_dwdb<16>);
-  HIP_CHECK_LN(hipGetLastError());
+  dispatch_cpt<1, 2, 3, 4, 8, 16>(
+      ecpt, [&](auto K) { launch_dw(k_ln_bwd_dwdb<K()>); });
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

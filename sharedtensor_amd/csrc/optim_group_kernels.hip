@@ -32,19 +32,11 @@
 #include <string>
 #include <type_traits>
 
+#include "device_util.h"
 #include "hip_api.h"
 #include "optim_step.h"
 
 namespace shamd {
-
-#define HIP_CHECK(expr)                                                    \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e) + " at " __FILE__ ":" + \
-                               std::to_string(__LINE__));                  \
-  } while (0)
 
 static_assert(GROUP_TILE == 256, "one element per thread of a 256-block");
 

@@ -9,19 +9,9 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device_util.h"
 
 namespace shamd {
-
-__device__ __forceinline__ float bf16_to_f32(uint16_t u) {
-  return __uint_as_float(static_cast<uint32_t>(u) << 16);
-}
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;  // NaN
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round-to-nearest-even
-  return static_cast<uint16_t>(u >> 16);
-}
 
 // a + b rounded on its own.  The optimizers' u = -lr * (...) would otherwise
 // be contracted into the shadow's old + u, which then is no longer the

@@ -27,30 +27,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"
 
 namespace shamd {
-
-#define HIP_CHECK_RP(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ float rp_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float rp_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint16_t rp_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
 
 // (o1, o2) = rotation of (x1, x2) by the angle whose cos/sin are c/s, as
 // bf16 pair bits.  o1 = rn(x1*c) - rn(x2*s), o2 = rn(x1*s) + rn(x2*c): no
@@ -64,8 +44,7 @@ static __device__ __forceinline__ uint32_t rp_rot(float x1, float x2, float c,
   float e = x2 * c;
   float o1 = a - b;
   float o2 = d + e;
-  return static_cast<uint32_t>(rp_bf16(o1)) |
-         (static_cast<uint32_t>(rp_bf16(o2)) << 16);
+  return bf16x2_pack(o1, o2);
 }
 
 constexpr int RP_BLOCK = 256;
@@ -117,14 +96,14 @@ k_rope_qk(RopeSide q, RopeSide k, const float* __restrict__ cos,
           s.x = -s.x; s.y = -s.y; s.z = -s.z; s.w = -s.w;
         }
         uint4 o;
-        o.x = rp_rot(rp_lo(x.x), rp_hi(x.x), c.x, s.x);
-        o.y = rp_rot(rp_lo(x.y), rp_hi(x.y), c.y, s.y);
-        o.z = rp_rot(rp_lo(x.z), rp_hi(x.z), c.z, s.z);
-        o.w = rp_rot(rp_lo(x.w), rp_hi(x.w), c.w, s.w);
+        o.x = rp_rot(bf16x2_lo(x.x), bf16x2_hi(x.x), c.x, s.x);
+        o.y = rp_rot(bf16x2_lo(x.y), bf16x2_hi(x.y), c.y, s.y);
+        o.z = rp_rot(bf16x2_lo(x.z), bf16x2_hi(x.z), c.z, s.z);
+        o.w = rp_rot(bf16x2_lo(x.w), bf16x2_hi(x.w), c.w, s.w);
         *reinterpret_cast<uint4*>(op) = o;
       } else {
-        float x1 = __uint_as_float(static_cast<uint32_t>(ip[0]) << 16);
-        float x2 = __uint_as_float(static_cast<uint32_t>(ip[1]) << 16);
+        float x1 = bf16_to_f32(ip[0]);
+        float x2 = bf16_to_f32(ip[1]);
         float c = cos[tab];
         float s = INVERSE ? -sin[tab] : sin[tab];
         uint32_t o = rp_rot(x1, x2, c, s);
@@ -164,7 +143,7 @@ static void rp_launch(const RopeSide& q, const RopeSide& k, const float* cos,
                      static_cast<uint32_t>(Hq), static_cast<uint32_t>(nchunk),
                      shift, static_cast<uint32_t>(W),
                      static_cast<uint32_t>(TW), D / 2);
-  HIP_CHECK_RP(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_rope_qk(const void* q, const void* k, void* q_out, void* k_out,

@@ -13,34 +13,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_util.h"
 #include "hip_api.h"
 
 namespace shamd {
 
-#define HIP_CHECK_SW(expr)                                                 \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e));                     \
-  } while (0)
-
-static __device__ __forceinline__ float sw_lo(uint32_t p) {
-  return __uint_as_float(p << 16);
-}
-static __device__ __forceinline__ float sw_hi(uint32_t p) {
-  return __uint_as_float(p & 0xFFFF0000u);
-}
-static __device__ __forceinline__ uint16_t sw_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-static __device__ __forceinline__ uint32_t sw_pack(float lo, float hi) {
-  return static_cast<uint32_t>(sw_bf16(lo)) |
-         (static_cast<uint32_t>(sw_bf16(hi)) << 16);
-}
 static __device__ __forceinline__ float sw_sigmoid(float x) {
   return 1.0f / (1.0f + __expf(-x));
 }
@@ -61,9 +38,9 @@ __global__ void k_swiglu_fwd(const uint4* __restrict__ x1,
     uint32_t* op = &o.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float a0 = sw_lo(ap[k]), a1 = sw_hi(ap[k]);
+      float a0 = bf16x2_lo(ap[k]), a1 = bf16x2_hi(ap[k]);
       float s0 = a0 * sw_sigmoid(a0), s1 = a1 * sw_sigmoid(a1);
-      op[k] = sw_pack(s0 * sw_lo(bp[k]), s1 * sw_hi(bp[k]));
+      op[k] = bf16x2_pack(s0 * bf16x2_lo(bp[k]), s1 * bf16x2_hi(bp[k]));
     }
     y[i] = o;
   }
@@ -87,29 +64,21 @@ __global__ void k_swiglu_bwd(const uint4* __restrict__ dy,
     uint32_t* o3p = &o3.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float g0 = sw_lo(gp[k]), g1 = sw_hi(gp[k]);
-      float a0 = sw_lo(ap[k]), a1 = sw_hi(ap[k]);
-      float b0 = sw_lo(bp[k]), b1 = sw_hi(bp[k]);
+      float g0 = bf16x2_lo(gp[k]), g1 = bf16x2_hi(gp[k]);
+      float a0 = bf16x2_lo(ap[k]), a1 = bf16x2_hi(ap[k]);
+      float b0 = bf16x2_lo(bp[k]), b1 = bf16x2_hi(bp[k]);
       float sg0 = sw_sigmoid(a0), sg1 = sw_sigmoid(a1);
       // the bounded factors silu'(a) and silu(a) first: dy * x3 or dy * x1
       // alone can overflow to inf where they have underflowed to 0, and
       // inf * 0 is NaN where the gradient is 0
       float d0 = sg0 * (1.f + a0 * (1.f - sg0));
       float d1 = sg1 * (1.f + a1 * (1.f - sg1));
-      o1p[k] = sw_pack(g0 * (b0 * d0), g1 * (b1 * d1));
-      o3p[k] = sw_pack(g0 * (a0 * sg0), g1 * (a1 * sg1));
+      o1p[k] = bf16x2_pack(g0 * (b0 * d0), g1 * (b1 * d1));
+      o3p[k] = bf16x2_pack(g0 * (a0 * sg0), g1 * (a1 * sg1));
     }
     dx1[i] = o1;
     dx3[i] = o3;
   }
-}
-
-// uint4 loads and stores: every pointer must be 16-byte aligned (the Python
-// wrapper clones an offset view that is not).
-static void sw_check_align(const void* p, const char* what) {
-  if (reinterpret_cast<uintptr_t>(p) & 15u)
-    throw std::runtime_error(std::string("swiglu: ") + what +
-                             " is not 16-byte aligned");
 }
 
 static inline int sw_grid(int64_t n8) {
@@ -120,26 +89,27 @@ static inline int sw_grid(int64_t n8) {
 void hip_swiglu_fwd(const void* x1, const void* x3, void* y, int64_t n,
                     hipStream_t s) {
   if (n % 8) throw std::runtime_error("swiglu: n must be a multiple of 8");
-  sw_check_align(x1, "x1");
-  sw_check_align(x3, "x3");
-  sw_check_align(y, "y");
+  // uint4 loads and stores (the Python wrapper clones an offset view)
+  check_align(x1, 16, "swiglu", "x1");
+  check_align(x3, 16, "swiglu", "x3");
+  check_align(y, 16, "swiglu", "y");
   if (n <= 0) return;
   int64_t n8 = n / 8;
   hipLaunchKernelGGL(k_swiglu_fwd, dim3(sw_grid(n8)), dim3(SW_BLOCK), 0, s,
                      static_cast<const uint4*>(x1),
                      static_cast<const uint4*>(x3), static_cast<uint4*>(y),
                      n8);
-  HIP_CHECK_SW(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void hip_swiglu_bwd(const void* dy, const void* x1, const void* x3, void* dx1,
                     void* dx3, int64_t n, hipStream_t s) {
   if (n % 8) throw std::runtime_error("swiglu: n must be a multiple of 8");
-  sw_check_align(dy, "dy");
-  sw_check_align(x1, "x1");
-  sw_check_align(x3, "x3");
-  sw_check_align(dx1, "dx1");
-  sw_check_align(dx3, "dx3");
+  check_align(dy, 16, "swiglu", "dy");
+  check_align(x1, 16, "swiglu", "x1");
+  check_align(x3, 16, "swiglu", "x3");
+  check_align(dx1, 16, "swiglu", "dx1");
+  check_align(dx3, 16, "swiglu", "dx3");
   if (n <= 0) return;
   int64_t n8 = n / 8;
   hipLaunchKernelGGL(k_swiglu_bwd, dim3(sw_grid(n8)), dim3(SW_BLOCK), 0, s,
@@ -147,7 +117,7 @@ void hip_swiglu_bwd(const void* dy, const void* x1, const void* x3, void* dx1,
                      static_cast<const uint4*>(x1),
                      static_cast<const uint4*>(x3), static_cast<uint4*>(dx1),
                      static_cast<uint4*>(dx3), n8);
-  HIP_CHECK_SW(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace shamd

@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import _core
+from .alignment import aligned
 
 # fp32 scratch for the column-sum partials, one per (device, stream); the
 # kernels overwrite what they read, so it is never zeroed
@@ -50,10 +51,8 @@ def _bf16_cuda(*tensors) -> None:
 
 
 def _vec(t: torch.Tensor) -> torch.Tensor:
-    """Contiguous and 16-byte aligned.  contiguous() keeps an offset view of
-    a larger buffer as it is; a copy aligns it."""
-    t = t.contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
+    """Contiguous and 16-byte aligned: the kernels load uint4."""
+    return aligned(t.contiguous(), 16)
 
 
 class _BiasGeluFn(torch.autograd.Function):

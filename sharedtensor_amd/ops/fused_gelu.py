@@ -11,18 +11,13 @@ from __future__ import annotations
 import torch
 
 from .. import _core
-
-
-def _vec_aligned(t):
-    """The kernels load uint4.  contiguous() keeps an offset view of a larger
-    buffer as it is; a copy aligns it to 16 bytes."""
-    return t.clone() if t.data_ptr() % 16 else t
+from .alignment import aligned
 
 
 class _FusedGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        x = _vec_aligned(x.contiguous())
+        x = aligned(x.contiguous(), 16)  # the kernels load uint4
         y = torch.empty_like(x)
         s = torch.cuda.current_stream(x.device).cuda_stream
         _core.gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), s)
@@ -32,7 +27,7 @@ class _FusedGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        dy = _vec_aligned(dy.contiguous())
+        dy = aligned(dy.contiguous(), 16)
         dx = torch.empty_like(x)
         s = torch.cuda.current_stream(x.device).cuda_stream
         _core.gelu_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), s)

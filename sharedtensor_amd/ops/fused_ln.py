@@ -22,6 +22,7 @@ from __future__ import annotations
 import torch
 
 from .. import _core
+from .alignment import aligned
 
 MAX_C = 4096  # per-thread register accumulators in the dw/db kernel
 
@@ -39,14 +40,6 @@ def _wave_path(C: int, *tensors) -> bool:
 
 def _ptr(t) -> int:
     return t.data_ptr() if t is not None else 0
-
-
-def _pair_aligned(t):
-    """The block-per-row kernels load bf16 pairs as uint32.  contiguous()
-    keeps an offset view of a larger buffer as it is; a copy aligns it."""
-    if t is not None and t.data_ptr() % 4:
-        return t.clone()
-    return t
 
 
 def _partials_for(device, C: int, stream: int) -> torch.Tensor:
@@ -108,9 +101,10 @@ class _FusedLayerNormFn(torch.autograd.Function):
             _, y, mean, rstd = _wave_fwd(x, None, None, weight, bias, eps)
             ctx.save_for_backward(x, weight, mean, rstd)
             return y
-        x = _pair_aligned(x)
-        weight = _pair_aligned(weight)
-        bias = _pair_aligned(bias)
+        # the block-per-row kernels load bf16 pairs as uint32
+        x = aligned(x, 4)
+        weight = aligned(weight, 4)
+        bias = aligned(bias, 4)
         y = torch.empty_like(x)
         mean = torch.empty(R, dtype=torch.float32, device=x.device)
         rstd = torch.empty(R, dtype=torch.float32, device=x.device)
@@ -132,7 +126,7 @@ class _FusedLayerNormFn(torch.autograd.Function):
             dx, dgamma, dbeta, _ = _wave_bwd(dy, x, w, mean, rstd, None,
                                              False)
             return dx, dgamma, dbeta if ctx.has_bias else None, None
-        dy = _pair_aligned(dy)
+        dy = aligned(dy, 4)
         dx = torch.empty_like(x)
         dwdb = torch.zeros(2 * C, dtype=torch.float32, device=x.device)
         dgamma, dbeta = dwdb[:C], dwdb[C:]

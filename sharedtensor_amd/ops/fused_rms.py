@@ -21,21 +21,17 @@ import os
 import torch
 
 from .. import _core
+from .alignment import aligned
 
 MAX_C = 4096  # per-thread register accumulators in the dgamma kernel
-
-
-def _pair_aligned(t):
-    """The block-per-row kernels load bf16 pairs as uint32.  contiguous()
-    keeps an offset view of a larger buffer as it is; a copy aligns it."""
-    return t.clone() if t.data_ptr() % 4 else t
 
 
 class _FusedRMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
-        x = _pair_aligned(x.contiguous())
-        weight = _pair_aligned(weight)
+        # the block-per-row kernels load bf16 pairs as uint32
+        x = aligned(x.contiguous(), 4)
+        weight = aligned(weight, 4)
         C = x.shape[-1]
         R = x.numel() // C
         y = torch.empty_like(x)
@@ -49,7 +45,7 @@ class _FusedRMSNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, rstd = ctx.saved_tensors
-        dy = _pair_aligned(dy.contiguous())
+        dy = aligned(dy.contiguous(), 4)
         C = x.shape[-1]
         R = x.numel() // C
         dx = torch.empty_like(x)

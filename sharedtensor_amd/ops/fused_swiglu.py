@@ -9,19 +9,15 @@ import os
 import torch
 
 from .. import _core
-
-
-def _vec_aligned(t):
-    """The kernels load uint4.  contiguous() keeps an offset view of a larger
-    buffer as it is; a copy aligns it to 16 bytes."""
-    return t.clone() if t.data_ptr() % 16 else t
+from .alignment import aligned
 
 
 class _FusedSwiGLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x3):
-        x1 = _vec_aligned(x1.contiguous())
-        x3 = _vec_aligned(x3.contiguous())
+        # the kernels load uint4
+        x1 = aligned(x1.contiguous(), 16)
+        x3 = aligned(x3.contiguous(), 16)
         y = torch.empty_like(x1)
         s = torch.cuda.current_stream(x1.device).cuda_stream
         _core.swiglu_fwd(x1.data_ptr(), x3.data_ptr(), y.data_ptr(),
@@ -32,7 +28,7 @@ class _FusedSwiGLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x1, x3 = ctx.saved_tensors
-        dy = _vec_aligned(dy.contiguous())
+        dy = aligned(dy.contiguous(), 16)
         dx1 = torch.empty_like(x1)
         dx3 = torch.empty_like(x3)
         s = torch.cuda.current_stream(x1.device).cuda_stream

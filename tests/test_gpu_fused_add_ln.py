@@ -139,7 +139,9 @@ VARIANTS = [(d, r, b, db) for d in (True, False) for r in (True, False)
             for b in (True, False) for db in (True, False) if d or not db]
 
 
-@pytest.mark.parametrize("R,C", [(1000, 768), (8195, 512), (5, 64)])
+# 256 and 1024: the narrowest and the widest wave-per-row instantiation
+@pytest.mark.parametrize("R,C", [(1000, 768), (8195, 512), (5, 64), (5, 256),
+                                 (5, 1024)])
 @pytest.mark.parametrize("has_delta,has_dres,has_bias,has_dbias", VARIANTS)
 def test_variants(R, C, has_delta, has_dres, has_bias, has_dbias):
     check(R, C, has_delta, has_dres, has_bias, has_dbias)

@@ -115,8 +115,9 @@ def test_shapes(R, C):
     check(R, C, has_delta=True, has_dres=True)
 
 
+# 1024, 2560 and 3584: the multiples of 512 that WIDTHS leaves out
 @pytest.mark.parametrize("R,C", [(1000, 2048), (RAGGED, 512), (5, 4096),
-                                 (5, 64)])
+                                 (5, 64), (5, 1024), (5, 2560), (5, 3584)])
 @pytest.mark.parametrize("has_delta,has_dres",
                          [(True, False), (False, True), (False, False)])
 def test_variants(R, C, has_delta, has_dres):
