@@ -1,6 +1,7 @@
 """fp64 references and derived error bounds for the bf16 model kernels
-(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU) and, at the end
-of the file, for the fused fp32 optimizers (AdamW, SGD momentum).
+(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU), for the fused
+fp32 optimizers (AdamW, SGD momentum) and, at the end of the file, for the
+fused cross-entropy kernels.
 
 Reference: the same formula evaluated in fp64 on the bf16 inputs; backward
 references use fp64 statistics, never the kernel's saved mean / rstd.
@@ -227,15 +228,20 @@ def ln_slack(x, w, b=None, dy=None, eps=EPS32):
 # ------------------------------------------------- kernel-order emulation
 
 def emu_block_sum(v: np.ndarray) -> np.ndarray:
-    """The kernels' block_sum in fp32: v is (..., 256) per-thread partials;
-    a shuffle-down tree inside each 64-lane wave, then ((w0+w1)+w2)+w3."""
-    a = v.astype(np.float32).reshape(v.shape[:-1] + (4, 64)).copy()
+    """The kernels' block_sum in fp32: v is (..., BLK) per-thread partials
+    (BLK = 256, 512 or 1024); a shuffle-down tree inside each 64-lane wave,
+    then the wave results in wave order, ((w0+w1)+w2)+w3 ..."""
+    waves = v.shape[-1] // 64
+    a = v.astype(np.float32).reshape(v.shape[:-1] + (waves, 64)).copy()
     w = 32
     while w:
         a[..., :w] = a[..., :w] + a[..., w:2 * w]
         w >>= 1
     l = a[..., 0]
-    return ((l[..., 0] + l[..., 1]) + l[..., 2]) + l[..., 3]
+    t = l[..., 0]
+    for i in range(1, waves):
+        t = t + l[..., i]
+    return t
 
 
 def emu_ln_stats(x: torch.Tensor, one_pass: bool, eps=EPS32):
@@ -612,3 +618,364 @@ def bias_corrections(b1, b2, step):
     f = np.float32
     return (float(f(1) / (f(1) - np.power(f(b1), f(step)))),
             float(f(1) / (f(1) - np.power(f(b2), f(step)))))
+
+
+# ------------------------------------------------------ fused cross-entropy
+#
+# The kernels (csrc/ce_kernels.hip, ce_opts_kernels.hip, ce_common.h) evaluate
+# per row of bf16 logits, in fp32,
+#
+#   m    = max_j x_j                                   (exact)
+#   tot  = sum_j __expf(x_j - m)                       (>= 1, all terms >= 0)
+#   lse  = __logf(tot) + m
+#   loss = lse - x_t                                   (plain)
+#        = (1-eps)*(lse - x_t) + eps*(lse - sx/V) + z*lse*lse,  sx = sum_j x_j
+#   dx_j = g*inv_count*[(1 + 2*z*lse)*__expf(x_j - lse) - (1-eps)[j == t]
+#                       - eps/V]
+#
+# ce_formula is that chain in a chosen dtype; ce_slack bounds its fp32
+# evaluation in the kernels' reduction layout.
+#
+# Reduction depth of tot, n_ce(V, BLK, NCHUNK): a thread adds its chunks
+# serially (ceil(nbody / BLK) of them, at most NCHUNK in the register
+# kernels), each chunk is the 3-level tree of ce_expsum8, one more add brings
+# the edge element in, then block_sum<BLK>: 6 shuffle levels and BLK/64 - 1
+# LDS adds.  All terms are positive, so tot is off by at most n_ce * U
+# relative, plus the per-term error of the exp.
+#
+# Transcendentals.  __expf is the fast exp of the module docstring: the
+# argument x - m (or x - lse) is itself rounded (U*|arg|), the product with
+# log2(e) is rounded (U*|arg| again) and the exp2 and the constant get
+# EXP_ULPS = 3 ulps: relative error (2*|arg| + 3) * U.  For __logf neither the
+# HIP headers nor the installed documentation state an accuracy (the headers
+# only map it to the native log of the device library), so the figure is
+# reasoned, not looked up, and not calibrated on the kernel: the native log is
+# the hardware log2 (1 ulp by the instruction-set manual) times the fp32
+# constant ln 2 (half an ulp in the constant, half an ulp in the product),
+# 2 ulps in all; LOG_ULPS = 3 leaves one ulp for the hardware figure being
+# meant at the magnitude of the result.  The ulps are taken at
+# max(|log tot|, 1): close to tot = 1 the result is far smaller than the
+# exponent-plus-table evaluation's last place.  The gradient bound hardly
+# depends on LOG_ULPS: even 16 ulps on log(tot) <= 12 move exp(x - lse) by
+# less than 1e-5 relative against a bf16 ulp of 4e-3; only the fp32 loss and
+# lse bounds feel it.  A probability below the smallest normal fp32 may be
+# flushed to 0: ETA, scaled by the coefficient.
+#
+# Constants taken from documentation: U, ETA (IEEE formats), the hardware
+# log2 / exp2 ulp.  Derived here: n_ce, n_ce_sx, EXP_ULPS' use, LOG_ULPS, the
+# rounding counts CE_COEF_ROUNDINGS and CE_DIV_ULPS.
+
+EXP_ULPS = 3.0
+LOG_ULPS = 3.0
+# sx / V: correctly rounded by default; 3 covers a build whose fp32 division
+# is the 2.5-ulp one
+CE_DIV_ULPS = 3.0
+# roundings on the way to one gradient term, the longest path: g*inv_count
+# (1) and inv_count itself (1); a = gscale*(1 + 2*z*lse): z*lse, 1 + ., the
+# product (3); nb = gscale*(eps/V): quotient and product; the fused
+# multiply-add (1) and the subtraction of c at the target (1)
+CE_COEF_ROUNDINGS = 7
+
+
+def _ce_chunks(V, BLK, NCHUNK):
+    c = max(1, math.ceil((V // 8) / BLK))
+    return c if NCHUNK is None else min(c, NCHUNK)
+
+
+def n_ce(V, BLK, NCHUNK=None):
+    """Adds on the longest path of the exp-sum: NCHUNK None is the stride
+    loop of the two-pass kernels."""
+    return _ce_chunks(V, BLK, NCHUNK) + 3 + 1 + 6 + (BLK // 64 - 1)
+
+
+def n_ce_sx(V, BLK, NCHUNK=None):
+    """The same for sum_j x_j through ce_sum8: four dot2 per chunk, two fp32
+    roundings each, chained on the accumulator."""
+    return 8 * _ce_chunks(V, BLK, NCHUNK) + 1 + 6 + (BLK // 64 - 1)
+
+
+def _ce_layouts(V):
+    cap7 = 1024 * 7 * 8
+    return [(1024, 7 if V <= cap7 else 16), (256, None), (512, None)]
+
+
+def _ce_rows(x, t, ignore_index):
+    V = x.shape[1]
+    t = t.to(device=x.device, dtype=torch.int64)
+    in_range = (t >= 0) & (t < V)
+    ignored = (t == ignore_index) if ignore_index is not None \
+        else torch.zeros_like(in_range)
+    return t, in_range & ~ignored, ~in_range & ~ignored
+
+
+def f32_inv(n) -> float:
+    """fl32(1 / n) as the device computes it; inf at n = 0."""
+    with np.errstate(divide="ignore"):
+        return float(np.float32(1) / np.float32(n))
+
+
+def ce_formula(x, t, g=1.0, ignore_index=None, eps=0.0, z=0.0,
+               dtype=torch.float64, lse=None):
+    """Cross-entropy of bf16 logits x (R, V) with targets t (R,): per-row m,
+    lse and loss, the mean over the valid rows and dlogits for the upstream
+    gradient g.  Row kinds as cross_entropy_reference (ops/fused_ce.py): an
+    ignored row has loss 0, lse 0 and a +0 gradient row; an out-of-range,
+    not ignored one has loss NaN and a +0 gradient row.  `lse`: the fp32
+    row_lse a raw backward kernel is given; the gradient then uses it."""
+    R, V = x.shape
+    x = x.to(dtype)
+    eps, z, g = f32(eps), f32(z), f32(g)
+    t, valid, bad = _ce_rows(x, t, ignore_index)
+    m = x.max(-1).values
+    tot = torch.exp(x - m[:, None]).sum(-1)
+    own = torch.log(tot) + m
+    xt = x.gather(1, t.clamp(0, V - 1)[:, None]).squeeze(1)
+    if eps != 0.0 or z != 0.0:
+        sx = x.sum(-1)
+        loss = (1.0 - eps) * (own - xt) + eps * (own - sx / V) + z * own * own
+    else:
+        loss = own - xt
+    zero = torch.zeros((), dtype=dtype, device=x.device)
+    nan = torch.full((), float("nan"), dtype=dtype, device=x.device)
+    loss = torch.where(bad, nan, torch.where(valid, loss, zero))
+    n_valid = int(valid.sum())
+    inv = f32_inv(n_valid)
+    mean = loss.sum() / n_valid if n_valid else loss.sum() * nan
+    used = own if lse is None else lse.to(device=x.device, dtype=dtype)
+    p = torch.exp(x - used[:, None])
+    hot = torch.arange(V, device=x.device)[None, :] == t[:, None]
+    d = (1.0 + 2.0 * z * used)[:, None] * p - (1.0 - eps) * hot.to(dtype) \
+        - eps / V
+    d = torch.where(valid[:, None], (g * inv) * d if n_valid else d, zero)
+    return {"m": m, "lse": torch.where(valid, own, zero), "loss": loss,
+            "mean": mean, "dlogits": d, "valid": valid, "bad": bad,
+            "n_valid": n_valid}
+
+
+def ce_slack(x, t, g=1.0, ignore_index=None, eps=0.0, z=0.0, lse=None,
+             BLK=None, NCHUNK=None):
+    """Running-error bounds of ce_formula in fp32.  BLK / NCHUNK name the
+    kernel layout; without them the deepest of the layouts a call can take."""
+    R, V = x.shape
+    x = x.double()
+    eps, z, g = f32(eps), f32(z), f32(g)
+    if BLK is None:
+        n = max(n_ce(V, b, c) for b, c in _ce_layouts(V))
+        nsx = max(n_ce_sx(V, b, c) for b, c in _ce_layouts(V))
+    else:
+        n, nsx = n_ce(V, BLK, NCHUNK), n_ce_sx(V, BLK, NCHUNK)
+    t, valid, bad = _ce_rows(x, t, ignore_index)
+    fin = torch.isfinite(x)
+    zero = torch.zeros((), dtype=torch.float64, device=x.device)
+
+    m = x.max(-1).values
+    xm = x - m[:, None]
+    e = torch.exp(xm)
+    tot = e.sum(-1)
+    axm = torch.where(fin, xm.abs(), zero)       # exp(-inf) is exactly 0
+    d_tot = (n * U + ((2 * axm + EXP_ULPS) * U * e).sum(-1) / tot
+             + V * ETA / tot)
+    logt = torch.log(tot)
+    own = logt + m
+    d_lse = d_tot + LOG_ULPS * U * logt.abs().clamp_min(1.0) + U * own.abs()
+    xt = x.gather(1, t.clamp(0, V - 1)[:, None]).squeeze(1)
+    if eps != 0.0 or z != 0.0:
+        sx = x.sum(-1)
+        sabs = torch.where(fin, x.abs(), zero).sum(-1)
+        d_sx = nsx * U * sabs + V * ETA
+        A = (1.0 - eps) * (own - xt)
+        B = eps * (own - sx / V)
+        C = z * own * own
+        d_loss = ((1.0 - eps) * d_lse + 3 * U * A.abs()
+                  + eps * (d_lse + d_sx / V + CE_DIV_ULPS * U * (sx / V).abs()
+                           + U * (own - sx / V).abs()) + U * B.abs()
+                  + 2 * z * own.abs() * d_lse + 2 * U * C.abs()
+                  + 2 * U * (A.abs() + B.abs() + C.abs()))
+    else:
+        d_loss = d_lse          # the subtraction's rounding is assert_f32's
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=x.device)
+    d_loss = torch.where(torch.isfinite(d_loss), d_loss, inf)
+    d_loss = torch.where(valid, d_loss, zero)
+    d_lse_out = torch.where(valid, d_lse, zero)
+
+    ref = ce_formula(x, t, g, ignore_index, eps, z, lse=None)
+    n_valid = ref["n_valid"]
+    if n_valid and not bool(bad.any()):
+        lv = torch.where(valid, ref["loss"], zero)
+        d_mean = ((d_loss + U * lv.abs()).sum() / n_valid
+                  + (R + 3) * U * lv.abs().sum() / n_valid
+                  + 2 * U * ref["mean"].abs())
+    else:
+        d_mean = zero
+
+    used = own if lse is None else lse.to(device=x.device).double()
+    d_used = d_lse if lse is None else torch.zeros_like(d_lse)
+    xl = x - used[:, None]
+    p = torch.exp(xl)
+    axl = torch.where(fin, xl.abs(), zero)
+    dp = p * (d_used[:, None] + (2 * axl + EXP_ULPS) * U) + ETA
+    gs = abs(g * f32_inv(n_valid)) if n_valid else 0.0
+    a = gs * (1.0 + 2.0 * z * used.abs())[:, None]
+    hot = (torch.arange(V, device=x.device)[None, :] == t[:, None]).double()
+    mag = a * p + gs * eps / V + gs * (1.0 - eps) * hot
+    d = (a * dp + gs * 2.0 * z * d_used[:, None] * p
+         + CE_COEF_ROUNDINGS * U * mag)
+    d = torch.where(valid[:, None], d, zero)
+    return {"m": torch.zeros_like(m), "lse": d_lse_out, "loss": d_loss,
+            "mean": d_mean, "dlogits": d}
+
+
+def assert_f32_rows(got, ref, slack, op, out, family):
+    """assert_f32 for per-row values that may be NaN or infinite by design
+    (an out-of-range target; a -inf logit under label smoothing): the same
+    rows must be NaN, infinities must match, the rest meets the bound."""
+    got, ref = got.double().cpu(), ref.double().cpu()
+    slack = slack.double().cpu() if torch.is_tensor(slack) else slack
+    assert torch.equal(torch.isnan(got), torch.isnan(ref)), \
+        f"{op} {out} [{family}]: NaN rows differ: got {got}, ref {ref}"
+    inf = torch.isinf(ref)
+    assert torch.equal(got[inf], ref[inf]), f"{op} {out} [{family}]: inf rows"
+    fin = torch.isfinite(ref)
+    s = slack[fin] if torch.is_tensor(slack) and slack.dim() else slack
+    return assert_f32(got[fin], ref[fin], s, op, out, family)
+
+
+def is_plus_zero(t) -> bool:
+    """Every element is +0 bit for bit (bf16 or fp32)."""
+    bits = torch.int16 if t.element_size() == 2 else torch.int32
+    return not bool(t.contiguous().view(bits).any())
+
+
+def ce_check(got, x, t, op, family, g=1.0, ignore_index=None, eps=0.0,
+             z=0.0, lse=None, BLK=None, NCHUNK=None):
+    """Judge whatever of m / lse / loss / mean / dlogits `got` holds against
+    the fp64 reference, on the device x lives on.  Rows that are not valid
+    are held to their exact values.  Returns (ref, slack)."""
+    kw = dict(g=g, ignore_index=ignore_index, eps=eps, z=z, lse=lse)
+    ref = ce_formula(x, t, **kw)
+    slack = ce_slack(x, t, BLK=BLK, NCHUNK=NCHUNK, **kw)
+    valid, bad = ref["valid"], ref["bad"]
+    for k in ("m", "lse", "loss"):
+        if k not in got:
+            continue
+        v = got[k]
+        assert v.dtype == torch.float32 and v.shape == ref[k].shape, k
+        if k == "m":
+            assert torch.equal(v.double()[valid], ref[k][valid]), \
+                f"{op} m [{family}]: not the row maximum"
+            report(op, "m", family, 0.0, unit="of-slack")
+            continue
+        assert_f32_rows(v, ref[k], slack[k], op, k, family)
+        assert is_plus_zero(v[~valid & ~bad]), f"{op} {k}: ignored rows"
+        if k == "lse":
+            assert is_plus_zero(v[bad]), f"{op} lse: out-of-range rows"
+    if "mean" in got:
+        assert_f32_rows(got["mean"].reshape(1), ref["mean"].reshape(1),
+                        slack["mean"].reshape(1), op, "mean", family)
+    if "dlogits" in got:
+        d = got["dlogits"]
+        assert d.dtype == torch.bfloat16 and d.shape == ref["dlogits"].shape
+        assert_bf16(d, ref["dlogits"], slack["dlogits"], op, "dlogits",
+                    family)
+        assert is_plus_zero(d[~valid]), f"{op} dlogits: rows not valid"
+    return ref, slack
+
+
+def seam_targets(R, V, offset=0):
+    """Targets at element 0, at V-1, in a head and in a tail element of rows
+    that have one (`offset` = element offset of the matrix from a 16-byte
+    boundary); random elsewhere.  int64, on the CPU."""
+    g = torch.Generator().manual_seed(R * 7919 + V)
+    t = torch.randint(0, V, (R,), generator=g)
+    want = ["first", "last", "head", "tail"]
+    for r in range(R):
+        head = min((-(offset + r * V)) % 8, V)
+        tail = (V - head) % 8
+        if "head" in want and head > 1 and r > 0:
+            t[r] = head - 1
+            want.remove("head")
+        elif "tail" in want and tail > 1 and r > 0:
+            t[r] = V - tail
+            want.remove("tail")
+        elif "first" in want:
+            t[r] = 0
+            want.remove("first")
+        elif "last" in want:
+            t[r] = V - 1
+            want.remove("last")
+    return t
+
+
+CE_FAMILIES = ["randn3", "tiny", "wide", "flat", "peaked_target",
+               "peaked_other", "masked", "shifted", "neg_zero_mix"]
+
+
+def ce_inputs(family, R, V, seed=0, offset=0):
+    """bf16 logits (R, V) and int64 seam targets (R,), on the CPU."""
+    gen = torch.Generator().manual_seed(1000 * seed + 31 * R + V)
+    t = seam_targets(R, V, offset)
+    rows = torch.arange(R)
+    rn = torch.randn(R, V, generator=gen)
+    if family == "randn3":
+        x = rn * 3
+    elif family == "tiny":
+        x = rn * 1e-3
+    elif family == "wide":           # most exps underflow
+        x = rn * 30
+    elif family == "flat":           # one constant per row
+        x = (1.5 * (rows - R // 2).float())[:, None].expand(R, V).clone()
+    elif family in ("peaked_target", "peaked_other"):
+        x = rn * 0.1                 # 1 - p cancels at the peak
+        at = t if family == "peaked_target" else (t + V // 2) % V
+        x[rows, at] = 80.0
+    elif family == "masked":         # masked vocabulary
+        x = rn * 3
+        drop = torch.rand(R, V, generator=gen) < 0.5
+        drop[R // 2] = True          # a row with the target alone
+        drop[rows, t] = False
+        x[drop] = float("-inf")
+    elif family == "shifted":        # x - m exact, ulp(lse) = 2^-9
+        x = rn + 3e4
+    elif family == "neg_zero_mix":   # +-0 and bf16 subnormals
+        bits = torch.randint(0, 0x80, (R, V), generator=gen)
+        bits = torch.where(torch.rand(R, V, generator=gen) < 0.5,
+                           torch.zeros_like(bits), bits)
+        bits = bits | (torch.randint(0, 2, (R, V), generator=gen) << 15)
+        x = bits.to(torch.int32).to(torch.int16).view(torch.bfloat16).float()
+    else:
+        raise ValueError(family)
+    return x.to(torch.bfloat16), t
+
+
+def emu_ce_expsum(x, BLK=1024, NCHUNK=7):
+    """tot = sum_j exp(x_j - m) of each row of bf16 x (matrix on a 16-byte
+    boundary) in k_ce_fwd_grad<BLK, NCHUNK>'s thread layout and fp32 order:
+    thread t holds chunks t, t + BLK, ...; edge element e rides in thread
+    BLK - 1 - e; ce_expsum8's tree inside a chunk; then block_sum.  Returns
+    (m, tot, lse) in fp32."""
+    f = np.float32
+    xs = x.float().numpy().astype(f)
+    R, V = xs.shape
+    ms, tots = np.zeros(R, f), np.zeros(R, f)
+    for r in range(R):
+        row = xs[r]
+        head = min((-(r * V)) % 8, V)
+        nbody = (V - head) // 8
+        tail = V - head - 8 * nbody
+        assert nbody <= BLK * NCHUNK
+        m = row.max()
+        ex = np.exp((row - m).astype(f)).astype(f)
+        s = np.zeros(BLK, f)
+        edges = np.concatenate([ex[:head], ex[V - tail:]]) if tail \
+            else ex[:head]
+        s[BLK - 1 - np.arange(edges.size)] = edges
+        body = np.zeros((BLK * NCHUNK, 8), f)
+        body[:nbody] = ex[head:head + 8 * nbody].reshape(nbody, 8)
+        p = body[:, 0::2] + body[:, 1::2]
+        c8 = ((p[:, 0] + p[:, 1]) + (p[:, 2] + p[:, 3])).reshape(NCHUNK, BLK)
+        for k in range(NCHUNK):
+            s = np.where(k * BLK + np.arange(BLK) < nbody, s + c8[k], s)
+        ms[r], tots[r] = m, emu_block_sum(s.astype(f))
+    lse = (np.log(tots).astype(f) + ms).astype(f)
+    return (torch.from_numpy(ms), torch.from_numpy(tots),
+            torch.from_numpy(lse))

@@ -2,6 +2,7 @@
 import pytest
 import torch
 
+import kernel_bounds as kb
 from sharedtensor_amd.ops import fused_ce
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +27,9 @@ def test_fwd_bwd_matches_torch(R, V):
                                atol=2e-3)
     torch.testing.assert_close(lf.grad.float(), lt.grad.float(), rtol=5e-2,
                                atol=1e-4)
+    # element by element: 1 bf16 ulp + slack against the fp64 reference
+    kb.ce_check({"mean": loss_f.detach(), "dlogits": lf.grad}, logits,
+                targets, "fused_cross_entropy", f"R={R}/V={V}")
 
 
 def test_upstream_grad_scaling():

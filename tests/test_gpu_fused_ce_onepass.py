@@ -8,6 +8,7 @@ shapes and targets below aim at those seams.
 import pytest
 import torch
 
+import kernel_bounds as kb
 from sharedtensor_amd import _core
 from sharedtensor_amd.ops import fused_ce
 
@@ -24,25 +25,7 @@ def _seam_targets(R, V, offset=0):
     """Targets at element 0, at V-1, in a head and in a tail element of rows
     that have one (`offset` = element offset of the matrix from a 16-byte
     boundary); random elsewhere."""
-    g = torch.Generator().manual_seed(R * 7919 + V)
-    t = torch.randint(0, V, (R,), generator=g)
-    want = ["first", "last", "head", "tail"]
-    for r in range(R):
-        head = min((-(offset + r * V)) % 8, V)
-        tail = (V - head) % 8
-        if "head" in want and head > 1 and r > 0:
-            t[r] = head - 1
-            want.remove("head")
-        elif "tail" in want and tail > 1 and r > 0:
-            t[r] = V - tail
-            want.remove("tail")
-        elif "first" in want:
-            t[r] = 0
-            want.remove("first")
-        elif "last" in want:
-            t[r] = V - 1
-            want.remove("last")
-    return t.cuda()
+    return kb.seam_targets(R, V, offset).cuda()
 
 
 def _reference(logits, targets):
@@ -61,6 +44,9 @@ def _check(logits, targets):
     assert torch.isfinite(loss_f)
     torch.testing.assert_close(loss_f.float(), loss_t, **LOSS_TOL)
     torch.testing.assert_close(lf.grad.float(), grad_t, **GRAD_TOL)
+    # element by element: 1 bf16 ulp + slack against the fp64 reference
+    kb.ce_check({"mean": loss_f.detach(), "dlogits": lf.grad}, logits,
+                targets, "fused_cross_entropy", f"V={logits.shape[1]}")
     return loss_f.detach(), lf.grad
 
 

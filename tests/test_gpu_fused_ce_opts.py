@@ -11,6 +11,7 @@ import dataclasses
 import pytest
 import torch
 
+import kernel_bounds as kb
 from sharedtensor_amd import _core
 from sharedtensor_amd.ops import fused_ce
 from sharedtensor_amd.ops.fused_ce import cross_entropy_reference
@@ -38,25 +39,7 @@ def _seam_targets(R, V, offset=0):
     """Targets at element 0, at V-1, in a head and in a tail element of rows
     that have one (`offset` = element offset of the matrix from a 16-byte
     boundary); random elsewhere."""
-    g = torch.Generator().manual_seed(R * 7919 + V)
-    t = torch.randint(0, V, (R,), generator=g)
-    want = ["first", "last", "head", "tail"]
-    for r in range(R):
-        head = min((-(offset + r * V)) % 8, V)
-        tail = (V - head) % 8
-        if "head" in want and head > 1 and r > 0:
-            t[r] = head - 1
-            want.remove("head")
-        elif "tail" in want and tail > 1 and r > 0:
-            t[r] = V - tail
-            want.remove("tail")
-        elif "first" in want:
-            t[r] = 0
-            want.remove("first")
-        elif "last" in want:
-            t[r] = V - 1
-            want.remove("last")
-    return t.cuda()
+    return kb.seam_targets(R, V, offset).cuda()
 
 
 def _mask_rows(R, pattern):
@@ -107,6 +90,12 @@ def _check(logits, targets, **opts):
     torch.testing.assert_close(loss_f.float(), loss_t, equal_nan=True,
                                **LOSS_TOL)
     torch.testing.assert_close(grad_f.float(), grad_t, **GRAD_TOL)
+    # element by element: 1 bf16 ulp + slack against the fp64 reference
+    kb.ce_check({"mean": loss_f, "dlogits": grad_f}, logits, targets,
+                "fused_cross_entropy/opts", f"V={logits.shape[1]}",
+                ignore_index=opts.get("ignore_index"),
+                eps=opts.get("label_smoothing", 0.0),
+                z=opts.get("z_loss", 0.0))
     return loss_f, grad_f
 
 

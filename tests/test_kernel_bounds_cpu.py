@@ -273,3 +273,199 @@ def test_fp32_reference_meets_bound_sgd(g16):
     with pytest.raises(AssertionError):
         kb.assert_within(ref["u"][fin] * (1 + 1e-6), ref["u"][fin],
                          slack["u"][fin], "sgd", "u", "perturbed")
+
+
+# ----------------------------------------------------- fused cross-entropy
+
+CE_OPTION_SETS = {
+    "plain": dict(),
+    "ignore": dict(ignore_index=-100),
+    "eps": dict(eps=0.1),
+    "z": dict(z=1e-4),
+    "all": dict(ignore_index=-100, eps=0.1, z=1e-4),
+}
+GRAD_TOL = dict(rtol=5e-2, atol=1e-4)   # what the CE tests used to rely on
+
+
+def _ce_case(family, V, opts, R=8):
+    x, t = kb.ce_inputs(family, R, V)
+    if "ignore_index" in opts:
+        t = t.clone()
+        t[1::3] = -100
+    return x, t
+
+
+def _ce_judge(got, x, t, family, **opts):
+    """ce_check on fp32 CPU results; True when every output is accepted."""
+    try:
+        kb.ce_check(got, x, t, "ce-fp32cpu", family, **opts)
+    except AssertionError:
+        return False
+    return True
+
+
+def _ce_f32(x, t, **opts):
+    f = kb.ce_formula(x, t, dtype=torch.float32, **opts)
+    assert f["dlogits"].dtype == torch.float32
+    return {"lse": f["lse"], "loss": f["loss"], "mean": f["mean"],
+            "dlogits": _bf16(f["dlogits"])}, f
+
+
+@pytest.mark.parametrize("V", [13, 1003, 50257])
+@pytest.mark.parametrize("opts", CE_OPTION_SETS.values(),
+                         ids=CE_OPTION_SETS.keys())
+@pytest.mark.parametrize("family", kb.CE_FAMILIES)
+def test_fp32_reference_meets_bound_ce(family, opts, V):
+    x, t = _ce_case(family, V, opts)
+    got, f = _ce_f32(x, t, **opts)
+    got["m"] = f["m"]
+    for g in (1.0, 0.37):
+        if g != 1.0:
+            got = {"dlogits": _bf16(kb.ce_formula(
+                x, t, g=g, dtype=torch.float32, **opts)["dlogits"])}
+        # the tightest layout: the bound of every kernel is at least this
+        kb.ce_check(got, x, t, "ce-fp32cpu", f"{family}/V={V}", g=g,
+                    BLK=1024, NCHUNK=7, **opts)
+
+
+@pytest.mark.parametrize("family", kb.CE_FAMILIES)
+def test_kernel_order_expsum_meets_bound_ce(family):
+    """lse in the <1024, 7> thread layout and summation order at V = 50257,
+    and in the 16-chunk one (same row, fewer chunks used)."""
+    x, t = kb.ce_inputs(family, 8, 50257)
+    for nchunk in (7, 16):
+        m, tot, lse = kb.emu_ce_expsum(x, 1024, nchunk)
+        loss = (lse.double() - x.double().gather(1, t[:, None]).squeeze(1))
+        kb.ce_check({"m": m, "lse": lse, "loss": loss.float()}, x, t,
+                    "ce-emu", family, BLK=1024, NCHUNK=nchunk)
+
+
+def test_n_ce_counts_the_layouts():
+    # 7 chunks + expsum8 tree + edge + 6 shuffles + 15 LDS adds
+    assert kb.n_ce(50257, 1024, 7) == 7 + 3 + 1 + 6 + 15
+    assert kb.n_ce(13, 1024, 7) == 1 + 3 + 1 + 6 + 15
+    assert kb.n_ce(131072, 1024, 16) == 16 + 3 + 1 + 6 + 15
+    assert kb.n_ce(50257, 256) == 25 + 3 + 1 + 6 + 3
+    assert kb.n_ce(50257, 512) == 13 + 3 + 1 + 6 + 7
+    assert kb.n_ce_sx(50257, 1024, 7) == 56 + 1 + 6 + 15
+
+
+def test_ce_row_kinds_follow_the_reference_semantics():
+    x, t = kb.ce_inputs("randn3", 8, 13)
+    t = t.clone()
+    t[2], t[5], t[6] = -100, 13, -3
+    ref = kb.ce_formula(x, t, ignore_index=-100, eps=0.1, z=1e-4)
+    assert ref["n_valid"] == 5 and torch.isnan(ref["mean"])
+    assert ref["loss"][2] == 0 and ref["lse"][2] == 0
+    assert torch.isnan(ref["loss"][[5, 6]]).all()
+    assert kb.is_plus_zero(ref["dlogits"][[2, 5, 6]])
+    none = kb.ce_formula(x, torch.full((8,), -100), ignore_index=-100)
+    assert none["n_valid"] == 0 and torch.isnan(none["mean"])
+    assert kb.is_plus_zero(none["dlogits"])
+    assert kb.f32_inv(0) == float("inf")
+    # against the project's own statement of the semantics
+    from sharedtensor_amd.ops.fused_ce import cross_entropy_reference
+    t[5], t[6] = 1, 2
+    ref = kb.ce_formula(x, t, ignore_index=-100, eps=0.1, z=1e-4)
+    lt = x.float().requires_grad_(True)
+    want = cross_entropy_reference(lt, t, ignore_index=-100,
+                                   label_smoothing=0.1, z_loss=1e-4)
+    want.backward()
+    torch.testing.assert_close(ref["mean"].float(), want.detach(),
+                               rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(ref["dlogits"].float(), lt.grad, rtol=1e-4,
+                               atol=1e-7)
+
+
+def test_ce_bound_rejects_what_the_old_tolerance_accepted():
+    """A head element written as 0, and the -eps/V term dropped, both at
+    V = 50257: torch.testing.assert_close with the tolerance the CE tests
+    used lets them through; the bound does not."""
+    R, V = 8, 50257
+    x, t = kb.ce_inputs("randn3", R, V)
+    got, f = _ce_f32(x, t)
+    ref = kb.ce_formula(x, t)
+    assert _ce_judge(got, x, t, "randn3")
+    # row 1 starts 2 bytes past a 16-byte boundary: elements 0..6 are its head
+    j = 0 if int(t[1]) != 0 else 1
+    zeroed = dict(got, dlogits=got["dlogits"].clone())
+    zeroed["dlogits"][1, j] = 0.0
+    torch.testing.assert_close(zeroed["dlogits"].float(),
+                               ref["dlogits"].float(), **GRAD_TOL)
+    assert not _ce_judge(zeroed, x, t, "head-zero")
+
+    opts = dict(eps=0.1)
+    got, f = _ce_f32(x, t, **opts)
+    ref = kb.ce_formula(x, t, **opts)
+    assert _ce_judge(got, x, t, "randn3", **opts)
+    gs = kb.f32_inv(R)
+    no_b = dict(got, dlogits=_bf16(f["dlogits"] + gs * kb.f32(0.1) / V))
+    torch.testing.assert_close(no_b["dlogits"].float(),
+                               ref["dlogits"].float(), **GRAD_TOL)
+    assert not _ce_judge(no_b, x, t, "no-eps/V", **opts)
+
+
+def test_ce_bound_rejects_gradient_mutants():
+    R, V = 8, 50257
+    x, t = kb.ce_inputs("randn3", R, V)
+    got, f = _ce_f32(x, t)
+    gs = kb.f32_inv(R)
+
+    def mutant(d):
+        return dict(got, dlogits=_bf16(d))
+
+    # one body chunk's eight gradients doubled (row 0 has no head)
+    d = f["dlogits"].clone()
+    d[0, 8 * 1500:8 * 1501] *= 2
+    assert not _ce_judge(mutant(d), x, t, "chunk-doubled")
+    # the target's -1 one element late
+    d = f["dlogits"].clone()
+    r = next(i for i in range(R) if int(t[i]) + 1 < V)
+    d[r, t[r]] += gs
+    d[r, t[r] + 1] -= gs
+    assert not _ce_judge(mutant(d), x, t, "hot-late")
+    # inv_r = 1 / (R + 1)
+    d = f["dlogits"] * (R / (R + 1.0))
+    assert not _ce_judge(mutant(d), x, t, "inv_r")
+
+
+def test_ce_bound_rejects_dropped_z_factor():
+    """z = 1e-4 at lse ~ 15 makes the factor 1 + 2*z*lse = 1.003, three
+    quarters of the smallest relative bf16 ulp: together with the final
+    rounding it leaves the bound in a part of the elements."""
+    R, V = 8, 50257
+    x, t = kb.ce_inputs("randn3", R, V)
+    opts = dict(z=1e-4)
+    got, f = _ce_f32(x, t, **opts)
+    assert _ce_judge(got, x, t, "randn3", **opts)
+    plain = kb.ce_formula(x, t, dtype=torch.float32)["dlogits"]
+    ref = kb.ce_formula(x, t, **opts)
+    slack = kb.ce_slack(x, t, BLK=1024, NCHUNK=7, **opts)
+    bad, _ = kb.violations(_bf16(plain), ref["dlogits"], slack["dlogits"])
+    print(f"dropped 2*z*lse: {int(bad.sum())} of {bad.numel()} outside")
+    assert bad.sum() > 1000
+    assert not _ce_judge(dict(got, dlogits=_bf16(plain)), x, t, "no-z",
+                         **opts)
+
+
+def test_ce_bound_rejects_lse_and_mean_mutants():
+    R, V = 8, 50257
+    x, t = kb.ce_inputs("randn3", R, V)
+    got, f = _ce_f32(x, t)
+    # lse off by 2^-10 in one row, and the loss with it
+    for k in ("lse", "loss"):
+        off = {k: got[k].clone()}
+        off[k][5] += 2.0 ** -10
+        assert _ce_judge({k: got[k]}, x, t, "randn3")
+        assert not _ce_judge(off, x, t, k + "+2^-10")
+    # the mean over R instead of n_valid: in the scalar and in the gradient
+    opts = dict(ignore_index=-100)
+    x, t = _ce_case("randn3", V, opts)
+    got, f = _ce_f32(x, t, **opts)
+    n_valid = int((t != -100).sum())
+    assert n_valid == 5
+    assert _ce_judge(got, x, t, "randn3", **opts)
+    wrong = dict(got, mean=(f["loss"].sum() / R))
+    assert not _ce_judge(wrong, x, t, "mean/R", **opts)
+    wrong = dict(got, dlogits=_bf16(f["dlogits"] * (n_valid / R)))
+    assert not _ce_judge(wrong, x, t, "inv_count=1/R", **opts)
