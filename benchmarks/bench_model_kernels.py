@@ -3,7 +3,7 @@
 add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
 GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
 section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
-the fused bias-gradient section."""
+the fused bias-gradient section, `--only-attn` the attention forward."""
 import json
 import sys
 import time
@@ -164,6 +164,63 @@ def bench_bias_grad(out):
     out["torch_reduce3072_ms"] = round(t(lambda: dx.sum(0), iters=30), 4)
 
 
+def bench_attn(out, rounds=7, iters=20):
+    # ---- causal attention forward at the GPT-2-small B=64 shape (H=12,
+    # T=1024, D=64) on the strided q, k, v views of a packed (B, T, 3C)
+    # buffer: our kernel against the aten efficient-attention forward.  Arms
+    # interleaved round by round, device-event timed; median and range over
+    # the rounds.  103 GFLOP (causal half of 4 B H T^2 D) and 0.4 GB
+    # (q, k, v, out once) per call.
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from sharedtensor_amd.ops import fused_attn
+    B, H, T, D = 64, 12, 1024, 64
+    C = H * D
+    qkv = torch.randn(B, T, 3 * C, device="cuda").to(torch.bfloat16)
+    q, k, v = (x.view(B, T, H, D).transpose(1, 2)
+               for x in qkv.split(C, dim=2))
+    assert fused_attn.can_use(q, k, v)
+    o = torch.empty(B, T, H, D, dtype=torch.bfloat16, device="cuda")
+    lse = torch.empty(B, H, T, dtype=torch.float32, device="cuda")
+    pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
+           SDPBackend.MATH]
+
+    def aten():
+        with sdpa_kernel(pri, set_priority=True):
+            return torch.ops.aten._scaled_dot_product_efficient_attention(
+                q, k, v, None, True, 0.0, True)
+
+    arms = {"aten_efficient_attn_fwd": aten,
+            "fused_attn_fwd": lambda: fused_attn.attn_forward(
+                q, k, v, out=o, lse=lse)}
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for fn in arms.values():
+        timed(fn)
+    ms = {n: [] for n in arms}
+    for _ in range(rounds):
+        for n, fn in arms.items():
+            ms[n].append(timed(fn))
+    flop = 4 * B * H * T * T * D / 2
+    byts = 4 * B * H * T * D * 2
+    out["attn_shape"] = dict(B=B, H=H, T=T, D=D, rounds=rounds, iters=iters)
+    for n, xs in ms.items():
+        xs = sorted(xs)
+        med = xs[len(xs) // 2]
+        out[n + "_ms_median"] = round(med, 4)
+        out[n + "_ms_range"] = [round(xs[0], 4), round(xs[-1], 4)]
+        out[n + "_tflops"] = round(flop / med / 1e9, 1)
+        out[n + "_tbps"] = round(byts / med / 1e9, 2)
+
+
 def main():
     torch.cuda.set_device(0)
     s = torch.cuda.current_stream().cuda_stream
@@ -174,6 +231,10 @@ def main():
         return
     if "--only-bias-grad" in sys.argv[1:]:
         bench_bias_grad(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-attn" in sys.argv[1:]:
+        bench_attn(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-add-rms" in sys.argv[1:]:

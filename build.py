@@ -36,6 +36,7 @@ SOURCES = [
     "bias_grad_kernels.hip",
     "swiglu_kernels.hip",
     "rope_kernels.hip",
+    "attn_kernels.hip",
     "bindings.cpp",
 ]
 

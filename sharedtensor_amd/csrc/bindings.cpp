@@ -438,6 +438,26 @@ PYBIND11_MODULE(_core, m) {
                      reinterpret_cast<hipStream_t>(stream));
   });
 
+  // causal bf16 attention forward, head dim 64
+  m.def("attn_fwd_causal_hd64",
+        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out, uintptr_t lse,
+           int64_t B, int64_t H, int64_t T, std::array<int64_t, 3> q_strides,
+           std::array<int64_t, 3> k_strides, std::array<int64_t, 3> v_strides,
+           int64_t lse_stride, double scale, uintptr_t stream) {
+          hip_attn_fwd_causal_hd64(
+              reinterpret_cast<const void*>(q),
+              reinterpret_cast<const void*>(k),
+              reinterpret_cast<const void*>(v), reinterpret_cast<void*>(out),
+              reinterpret_cast<float*>(lse), B, H, T, q_strides.data(),
+              k_strides.data(), v_strides.data(), lse_stride,
+              static_cast<float>(scale),
+              reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
+        py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("T"),
+        py::arg("q_strides"), py::arg("k_strides"), py::arg("v_strides"),
+        py::arg("lse_stride"), py::arg("scale"), py::arg("stream"));
+
   // fused bf16 cross-entropy
   m.def("ce_fwd", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,
                      uintptr_t row_m, uintptr_t row_lse, int64_t R, int64_t V,

@@ -319,4 +319,18 @@ void hip_pack3_colsum(const void* s0, const void* s1, const void* s2,
                       void* dst, void* db, float* partial, int64_t R,
                       int64_t C, hipStream_t s);
 
+// Causal bf16 attention forward, head dim 64 (attn_kernels.hip).  q, k, v are
+// read in place through element strides {batch, token, head} (each a
+// multiple of 8, pointers 16-byte aligned, the 64 elements of a head
+// contiguous); Tq == Tk == T, mask top-left aligned.  `out` is written as
+// contiguous (B, T, H, 64) bf16; `lse` (B, H, lse_stride >= T) fp32 receives
+// ln(sum exp(scale * score)) in its first T entries per row, the rest is left
+// alone.  scale > 0.  Throws on anything else.
+void hip_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
+                              void* out, float* lse, int64_t B, int64_t H,
+                              int64_t T, const int64_t* q_strides,
+                              const int64_t* k_strides,
+                              const int64_t* v_strides, int64_t lse_stride,
+                              float scale, hipStream_t s);
+
 }  // namespace shamd

@@ -62,10 +62,24 @@ FUSE_PROJ_BIAS = True
 FUSE_QKV_BIAS_GRAD = True
 FUSE_FC_BIAS_GRAD = False
 
+# Run the attention forward in our own kernel (ops/fused_attn.py: bf16, head
+# dim 64, causal) instead of the SDPA efficient-attention forward; the
+# backward stays the aten one, fed with our out and lse.  Numbers in
+# profiles/r08/.  SHTENS_FUSED_ATTN = 0 or 1 overrides the flag for an A/B
+# run; inputs the kernel does not take keep the SDPA path.
+FUSE_ATTN_FWD = True
+
 
 def _flag(env: str, default: bool) -> bool:
     v = os.environ.get(env)
     return default if v is None else v == "1"
+
+
+def _attn_ok(q, k, v) -> bool:
+    if not (_flag("SHTENS_FUSED_ATTN", FUSE_ATTN_FWD) and q.is_cuda):
+        return False
+    from ..ops import fused_attn
+    return fused_attn.can_use(q, k, v)
 
 
 def _bias_grad_ok(flag: bool, which: str, x, lin: nn.Linear) -> bool:
@@ -151,7 +165,10 @@ class CausalSelfAttention(nn.Module):
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
-        if x.is_cuda:
+        if _attn_ok(q, k, v):
+            from ..ops import fused_attn
+            y = fused_attn.fused_causal_attention(q, k, v)
+        elif x.is_cuda:
             # CK efficient-attention measured +16% end-to-end over the
             # default aotriton flash backend on MI355X at these shapes
             # (profiles/README.md), identical loss; priority list falls
