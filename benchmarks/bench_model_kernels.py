@@ -3,7 +3,8 @@
 add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
 GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
 section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
-the fused bias-gradient section, `--only-attn` the attention forward."""
+the fused bias-gradient section, `--only-attn` the attention forward,
+`--only-wgrad` the split-K weight-gradient kernel."""
 import json
 import sys
 import time
@@ -221,6 +222,73 @@ def bench_attn(out, rounds=7, iters=20):
         out[n + "_tbps"] = round(byts / med / 1e9, 2)
 
 
+def load_tunableop():
+    """The checked-in TunableOp GEMM table, loaded as bench.py loads it."""
+    import os
+    import torch.cuda.tunable as tunable
+    fn = os.path.join(__file__.rsplit("/", 2)[0], "sharedtensor_amd",
+                      "tunableop_gfx950.csv")
+    tunable.enable(True)
+    tunable.tuning_enable(False)
+    tunable.read_file(fn)
+
+
+def bench_wgrad(out, rounds=7, iters=20, sweep=False):
+    # ---- dW = dY^T X of the four GPT-2-small layer Linears at M = 65536
+    # tokens: our split-K kernel plus its reduce pass against torch.mm with
+    # the tuned GEMM table.  Arms interleaved round by round, device-event
+    # timed; median and range over the rounds.  `--sweep` adds every kernel
+    # variant at 1 to 3 workgroups per CU.
+    from sharedtensor_amd.ops import fused_wgrad as fw
+    load_tunableop()
+    M = 65536
+    shapes = {"attn_qkv": (2304, 768), "attn_proj": (768, 768),
+              "mlp_fc": (3072, 768), "mlp_proj": (768, 3072)}
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    out["wgrad_setup"] = dict(M=M, rounds=rounds, iters=iters)
+    for name, (N, K) in shapes.items():
+        dy = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+        x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+        dw = torch.empty(N, K, dtype=torch.bfloat16, device="cuda")
+        dyt = dy.t()
+        arms = {"torch_mm": lambda: torch.mm(dyt, x, out=dw)}
+        variant = fw.TUNED.get((N, K), fw.DEFAULT_VARIANT)
+        arms["fused"] = lambda v=variant: fw.wgrad(dy, x, out=dw, variant=v)
+        if sweep:
+            for v, (tn, tk, _) in fw.VARIANTS.items():
+                tiles = (N // tn) * (K // tk)
+                for per_cu in (1, 2, 3):
+                    sp = fw.choose_split(tiles, M // fw.STEP, per_cu)
+                    arms[f"fused_v{v}_split{sp}"] = \
+                        lambda v=v, sp=sp: fw.wgrad(dy, x, out=dw, variant=v,
+                                                    split=sp)
+        for fn in arms.values():
+            timed(fn)
+        ms = {n: [] for n in arms}
+        for _ in range(rounds):
+            for n, fn in arms.items():
+                ms[n].append(timed(fn))
+        flop = 2.0 * M * N * K
+        rec = dict(N=N, K=K, wired=(N, K) in fw.TUNED, variant=variant)
+        for n, xs in ms.items():
+            xs = sorted(xs)
+            med = xs[len(xs) // 2]
+            rec[n] = dict(ms_median=round(med, 4),
+                          ms_range=[round(xs[0], 4), round(xs[-1], 4)],
+                          tflops=round(flop / med / 1e9, 1))
+        out["wgrad_" + name] = rec
+
+
 def main():
     torch.cuda.set_device(0)
     s = torch.cuda.current_stream().cuda_stream
@@ -235,6 +303,10 @@ def main():
         return
     if "--only-attn" in sys.argv[1:]:
         bench_attn(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-wgrad" in sys.argv[1:]:
+        bench_wgrad(out, sweep="--sweep" in sys.argv[1:])
         print(json.dumps(out, indent=1))
         return
     if "--only-add-rms" in sys.argv[1:]:

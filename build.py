@@ -37,6 +37,7 @@ SOURCES = [
     "swiglu_kernels.hip",
     "rope_kernels.hip",
     "attn_kernels.hip",
+    "wgrad_kernels.hip",
     "bindings.cpp",
 ]
 

@@ -458,6 +458,30 @@ PYBIND11_MODULE(_core, m) {
         py::arg("q_strides"), py::arg("k_strides"), py::arg("v_strides"),
         py::arg("lse_stride"), py::arg("scale"), py::arg("stream"));
 
+  // split-K bf16 weight gradient dW = dY^T X
+  m.def("wgrad_num_variants", &hip_wgrad_num_variants);
+  m.def("wgrad_tile", [](int variant) {
+    int tn = 0, tk = 0;
+    hip_wgrad_tile(variant, &tn, &tk);
+    return std::make_pair(tn, tk);
+  });
+  m.def("wgrad_bf16",
+        [](uintptr_t dy, uintptr_t x, uintptr_t dw, uintptr_t ws,
+           int64_t ws_floats, int64_t M, int64_t N, int64_t K, int64_t ldy,
+           int64_t ldx, int64_t ldw, int64_t split, int variant,
+           uintptr_t stream) {
+          hip_wgrad_bf16(reinterpret_cast<const void*>(dy),
+                         reinterpret_cast<const void*>(x),
+                         reinterpret_cast<void*>(dw),
+                         reinterpret_cast<float*>(ws), ws_floats, M, N, K, ldy,
+                         ldx, ldw, split, variant,
+                         reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("ws"),
+        py::arg("ws_floats"), py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("ldy"), py::arg("ldx"), py::arg("ldw"), py::arg("split"),
+        py::arg("variant"), py::arg("stream"));
+
   // fused bf16 cross-entropy
   m.def("ce_fwd", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,
                      uintptr_t row_m, uintptr_t row_lse, int64_t R, int64_t V,

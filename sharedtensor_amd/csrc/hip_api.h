@@ -333,4 +333,20 @@ void hip_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
                               const int64_t* v_strides, int64_t lse_stride,
                               float scale, hipStream_t s);
 
+// Split-K bf16 weight gradient dW[N, K] = dY[M, N]^T X[M, K]
+// (wgrad_kernels.hip), fp32 accumulation.  ldy, ldx, ldw are row strides in
+// elements (multiples of 8, pointers 16-byte aligned).  `variant` picks the
+// tile (hip_wgrad_tile); N and K must be multiples of it and M of 64.  Each
+// workgroup takes one tile and one of `split` contiguous ranges of 64-token
+// steps; with split > 1 the partial tiles go as fp32 through `ws`
+// (split * N * K floats, 16-byte aligned, written before it is read) and a
+// second kernel sums them in split order: no atomics, the same bits on every
+// call.  Runs on stream `s`.  Throws on anything else.
+int hip_wgrad_num_variants();
+void hip_wgrad_tile(int variant, int* tile_n, int* tile_k);
+void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
+                    int64_t ws_floats, int64_t M, int64_t N, int64_t K,
+                    int64_t ldy, int64_t ldx, int64_t ldw, int64_t split,
+                    int variant, hipStream_t s);
+
 }  // namespace shamd

@@ -69,10 +69,31 @@ FUSE_FC_BIAS_GRAD = False
 # run; inputs the kernel does not take keep the SDPA path.
 FUSE_ATTN_FWD = True
 
+# Take the weight gradient of the four layer Linears (attn.qkv, attn.proj,
+# mlp.fc, mlp.proj) from our split-K kernel (ops/fused_wgrad.py) instead of
+# the library's NT GEMM; forward, dX and the bias gradients stay where they
+# are.  Only the weight shapes in fused_wgrad.TUNED, the ones that won their
+# measurement, take it: attn.proj 0.099 ms against 0.173 ms for the tuned
+# library GEMM and attn.qkv 0.303 against 0.336.  mlp.fc (0.410 against
+# 0.394) and mlp.proj (0.414 against 0.404) lost and keep aten, as does
+# lm_head (large output, tied weight).  Numbers in profiles/r09/.
+# SHTENS_FUSED_WGRAD = 0 or 1 overrides the flag for an A/B run.
+FUSE_WGRAD = True
+
 
 def _flag(env: str, default: bool) -> bool:
     v = os.environ.get(env)
     return default if v is None else v == "1"
+
+
+def _linear(x, weight, bias=None):
+    """``F.linear``, with ``weight.grad`` from the split-K kernel for the
+    shapes it is wired for."""
+    if _flag("SHTENS_FUSED_WGRAD", FUSE_WGRAD) and x.is_cuda:
+        from ..ops import fused_wgrad
+        if fused_wgrad.wired(x, weight):
+            return fused_wgrad.linear_wgrad(x, weight, bias)
+    return F.linear(x, weight, bias)
 
 
 def _attn_ok(q, k, v) -> bool:
@@ -158,10 +179,11 @@ class CausalSelfAttention(nn.Module):
         if _bias_grad_ok(_flag("SHTENS_FUSED_QKV_BGRAD", FUSE_QKV_BIAS_GRAD),
                          "qkv", x, self.qkv):
             from ..ops import fused_bias_grad
-            qkv = F.linear(x, self.qkv.weight, self.qkv.bias.detach())
+            qkv = _linear(x, self.qkv.weight, self.qkv.bias.detach())
             q, k, v = fused_bias_grad.qkv_split_bgrad(qkv, self.qkv.bias)
         else:
-            q, k, v = self.qkv(x).split(C, dim=2)
+            q, k, v = _linear(x, self.qkv.weight,
+                              self.qkv.bias).split(C, dim=2)
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
@@ -182,8 +204,8 @@ class CausalSelfAttention(nn.Module):
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         y = y.transpose(1, 2).contiguous().view(B, T, C)
         if not proj_bias:  # the caller adds proj.bias (see Block)
-            return F.linear(y, self.proj.weight)
-        return self.proj(y)
+            return _linear(y, self.proj.weight)
+        return _linear(y, self.proj.weight, self.proj.bias)
 
 
 class MLP(nn.Module):
@@ -199,13 +221,14 @@ class MLP(nn.Module):
         if _bias_grad_ok(_flag("SHTENS_FUSED_GELU_BGRAD", FUSE_FC_BIAS_GRAD),
                          "gelu", x, self.fc):
             from ..ops import fused_bias_grad
-            pre = F.linear(x, self.fc.weight, self.fc.bias.detach())
+            pre = _linear(x, self.fc.weight, self.fc.bias.detach())
             h = fused_bias_grad.bias_gelu_bgrad(pre, self.fc.bias)
         else:
-            h = F.gelu(self.fc(x), approximate="tanh")
+            h = F.gelu(_linear(x, self.fc.weight, self.fc.bias),
+                       approximate="tanh")
         if not proj_bias:  # the caller adds proj.bias (see Block)
-            return F.linear(h, self.proj.weight)
-        return self.proj(h)
+            return _linear(h, self.proj.weight)
+        return _linear(h, self.proj.weight, self.proj.bias)
 
 
 class Block(nn.Module):
