@@ -31,7 +31,6 @@ SOURCES = [
     "add_ln_kernels.hip",
     "add_rms_kernels.hip",
     "ce_kernels.hip",
-    "ce_opts_kernels.hip",
     "gelu_kernels.hip",
     "bias_grad_kernels.hip",
     "swiglu_kernels.hip",
@@ -41,7 +40,7 @@ SOURCES = [
     "bindings.cpp",
 ]
 
-HEADERS = ["ce_common.h", "common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
+HEADERS = ["common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
            "optim_step.h", "rccl_transport.h"]
 
 

@@ -521,7 +521,7 @@ PYBIND11_MODULE(_core, m) {
   m.def("ce_fwd_grad_max_v", &hip_ce_fwd_grad_max_v);
 
   // fused bf16 cross-entropy with ignore_index / label smoothing / z-loss
-  // (ce_opts_kernels.hip).  state: 16 device bytes (hip_api.h CeOptState),
+  // (ce_kernels.hip, the masked row policies).  state: 16 device bytes (hip_api.h CeOptState),
   // written by ce_opts_scan.  ValueError for options out of range.
   m.attr("CE_OPT_STATE_BYTES") = static_cast<int>(sizeof(CeOptState));
   m.def("ce_opts_scan", [](uintptr_t targets, int64_t R, int64_t V,

@@ -150,4 +150,13 @@ inline void dispatch_cpt(int n, F&& f) {
                              std::to_string(n));
 }
 
+// Calls f(std::bool_constant<b>), for a bool template argument.
+template <typename F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
 }  // namespace shamd

@@ -210,8 +210,9 @@ void hip_add_rms_bwd(const void* dy, const void* x_new, const void* w,
                      void* dgamma, float* partial, int64_t R, int C,
                      hipStream_t s);
 
-// Fused bf16 cross-entropy (ce_kernels.hip): two-pass stats-only fwd saving
-// per-row (max, lse); bwd writes bf16 dlogits = g*(softmax - onehot), or in
+// Fused bf16 cross-entropy (ce_kernels.hip), plain mean over the R rows; the
+// targets are not checked.  Two-pass stats-only fwd saving per-row
+// (max, lse); bwd writes bf16 dlogits = g*(softmax - onehot), or in
 // skip_if_unit mode leaves the buffer alone when *gscale_dev == 1.
 void hip_ce_fwd(const void* logits, const int32_t* targets, float* loss,
                 float* row_m, float* row_lse, int64_t R, int64_t V,
@@ -228,8 +229,10 @@ void hip_ce_fwd_grad(const void* logits, const int32_t* targets, float* loss,
                      float* row_lse, void* dlogits, float inv_r, int64_t R,
                      int64_t V, hipStream_t s);
 
-// Fused cross-entropy with options (ce_opts_kernels.hip).  Row r is valid
-// when targets[r] != ignore_index (if has_ignore) and 0 <= targets[r] < V.
+// Fused cross-entropy with options: the same kernels (ce_kernels.hip) with a
+// row policy that masks rows and takes 1/count from the device.  Row r is
+// valid when targets[r] != ignore_index (if has_ignore) and
+// 0 <= targets[r] < V.
 // Per valid row:
 //   loss_r = (1-eps)*(lse - x_t) + eps*(lse - mean_j x_j) + z*lse^2
 //   dx_j   = g*inv_count*[(1 + 2*z*lse)*softmax_j - (1-eps)*[j==t] - eps/V]

@@ -12,11 +12,11 @@ a gradient, or for a vocabulary too large for one block's registers, forward
 is the stats-only two-pass kernel and backward the classic dlogits pass.
 SHTENS_CE_ONEPASS=0 forces that two-kernel path (for A/B measurements).
 
-Options (csrc/ce_opts_kernels.hip): ignore_index, label_smoothing and z_loss.
-With all three at their defaults the call is the path above, unchanged.
-Otherwise a one-block scan of the targets counts the valid rows on the device
-and the option kernels read 1/n_valid from device memory, so neither forward
-nor backward syncs with the host.  A row whose target equals ignore_index is
+Options: ignore_index, label_smoothing and z_loss, the same kernels with
+another row policy (csrc/ce_kernels.hip).  With all three at their defaults
+the call is the path above, unchanged.  Otherwise a one-block scan of the
+targets counts the valid rows on the device and the kernels read 1/n_valid
+from device memory, so neither forward nor backward syncs with the host.  A row whose target equals ignore_index is
 never read: it adds 0 to the loss and its dlogits row is exactly +0 (torch
 gives NaN gradients when such a row holds NaN; here they are zero).  A row
 whose target is out of range and is not ignore_index gets a zero dlogits row
@@ -39,34 +39,58 @@ def _onepass_enabled() -> bool:
 
 
 class _FusedCEFn(torch.autograd.Function):
+    """opts is None for the default call (plain kernels, 1/R, no scan and no
+    state tensor), else the option kernels' keyword arguments."""
+
     @staticmethod
-    def forward(ctx, logits, targets):
+    def forward(ctx, logits, targets, opts):
         logits = logits.contiguous()
         R, V = logits.shape
+        dev = logits.device
         t32 = targets.to(torch.int32).contiguous()
-        loss = torch.empty(R, dtype=torch.float32, device=logits.device)
-        row_lse = torch.empty(R, dtype=torch.float32, device=logits.device)
-        s = torch.cuda.current_stream(logits.device).cuda_stream
+        loss = torch.empty(R, dtype=torch.float32, device=dev)
+        row_lse = torch.empty(R, dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        ptrs = (logits.data_ptr(), t32.data_ptr(), loss.data_ptr())
+        ctx.opts = opts
+        if opts is None:
+            saved = ()
+        else:
+            # f32 inv_count | u32 n_valid | u32 n_bad | pad
+            state = torch.empty(_core.CE_OPT_STATE_BYTES // 4,
+                                dtype=torch.float32, device=dev)
+            _core.ce_opts_scan(t32.data_ptr(), R, V, opts["ignore_index"],
+                               opts["has_ignore"], state.data_ptr(), s)
+            saved = (state,)
         ctx.onepass = (ctx.needs_input_grad[0] and _onepass_enabled()
                        and V <= _core.ce_fwd_grad_max_v())
         if ctx.onepass:
             # same peak memory as allocating it in backward: both points
             # are the activation peak
             dlogits = torch.empty_like(logits)
-            _core.ce_fwd_grad(logits.data_ptr(), t32.data_ptr(),
-                              loss.data_ptr(), row_lse.data_ptr(),
-                              dlogits.data_ptr(), 1.0 / R, R, V, s)
-            ctx.save_for_backward(logits, t32, row_lse, dlogits)
+            saved += (dlogits,)
+            if opts is None:
+                _core.ce_fwd_grad(*ptrs, row_lse.data_ptr(),
+                                  dlogits.data_ptr(), 1.0 / R, R, V, s)
+            else:
+                _core.ce_opts_fwd_grad(*ptrs, row_lse.data_ptr(),
+                                       dlogits.data_ptr(), state.data_ptr(),
+                                       R, V, stream=s, **opts)
+        elif opts is None:
+            row_m = torch.empty(R, dtype=torch.float32, device=dev)
+            _core.ce_fwd(*ptrs, row_m.data_ptr(), row_lse.data_ptr(), R, V, s)
         else:
-            row_m = torch.empty(R, dtype=torch.float32, device=logits.device)
-            _core.ce_fwd(logits.data_ptr(), t32.data_ptr(), loss.data_ptr(),
-                         row_m.data_ptr(), row_lse.data_ptr(), R, V, s)
-            ctx.save_for_backward(logits, t32, row_lse)
-        return loss.mean()
+            _core.ce_opts_fwd(*ptrs, row_lse.data_ptr(), R, V, stream=s,
+                              **opts)
+        ctx.save_for_backward(logits, t32, row_lse, *saved)
+        if opts is None:
+            return loss.mean()
+        # mean over the valid rows; inv_count stays on the device
+        return loss.sum() * state[0]
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, t32, row_lse = ctx.saved_tensors[:3]
+        logits, t32, row_lse, *saved = ctx.saved_tensors
         R, V = logits.shape
         g = dloss.to(device=logits.device, dtype=torch.float32).contiguous()
         s = torch.cuda.current_stream(logits.device).cuda_stream
@@ -74,67 +98,15 @@ class _FusedCEFn(torch.autograd.Function):
         # it may be somebody's .grad (retain_graph=True)
         first = ctx.onepass
         ctx.onepass = False
-        dlogits = ctx.saved_tensors[3] if first else torch.empty_like(logits)
-        _core.ce_bwd(logits.data_ptr(), t32.data_ptr(), row_lse.data_ptr(),
-                     dlogits.data_ptr(), g.data_ptr(), 1.0 / R, R, V, s,
-                     skip_if_unit=first)
-        return dlogits, None
-
-
-class _FusedCEOptsFn(torch.autograd.Function):
-    """fused_cross_entropy with at least one option set."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, ignore_index, label_smoothing, z_loss):
-        logits = logits.contiguous()
-        R, V = logits.shape
-        dev = logits.device
-        t32 = targets.to(torch.int32).contiguous()
-        has_ignore = ignore_index is not None
-        opts = dict(ignore_index=ignore_index if has_ignore else 0,
-                    has_ignore=has_ignore, label_smoothing=label_smoothing,
-                    z_loss=z_loss)
-        loss = torch.empty(R, dtype=torch.float32, device=dev)
-        row_lse = torch.empty(R, dtype=torch.float32, device=dev)
-        # f32 inv_count | u32 n_valid | u32 n_bad | pad
-        state = torch.empty(_core.CE_OPT_STATE_BYTES // 4, dtype=torch.float32,
-                            device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _core.ce_opts_scan(t32.data_ptr(), R, V, opts["ignore_index"],
-                           has_ignore, state.data_ptr(), s)
-        ctx.opts = opts
-        ctx.onepass = (ctx.needs_input_grad[0] and _onepass_enabled()
-                       and V <= _core.ce_fwd_grad_max_v())
-        if ctx.onepass:
-            dlogits = torch.empty_like(logits)
-            _core.ce_opts_fwd_grad(logits.data_ptr(), t32.data_ptr(),
-                                   loss.data_ptr(), row_lse.data_ptr(),
-                                   dlogits.data_ptr(), state.data_ptr(), R, V,
-                                   stream=s, **opts)
-            ctx.save_for_backward(logits, t32, row_lse, state, dlogits)
+        dlogits = saved[-1] if first else torch.empty_like(logits)
+        ptrs = (logits.data_ptr(), t32.data_ptr(), row_lse.data_ptr(),
+                dlogits.data_ptr(), g.data_ptr())
+        if ctx.opts is None:
+            _core.ce_bwd(*ptrs, 1.0 / R, R, V, s, skip_if_unit=first)
         else:
-            _core.ce_opts_fwd(logits.data_ptr(), t32.data_ptr(),
-                              loss.data_ptr(), row_lse.data_ptr(), R, V,
-                              stream=s, **opts)
-            ctx.save_for_backward(logits, t32, row_lse, state)
-        # mean over the valid rows; inv_count stays on the device
-        return loss.sum() * state[0]
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, t32, row_lse, state = ctx.saved_tensors[:4]
-        R, V = logits.shape
-        g = dloss.to(device=logits.device, dtype=torch.float32).contiguous()
-        s = torch.cuda.current_stream(logits.device).cuda_stream
-        # as _FusedCEFn: the precomputed buffer serves the first backward only
-        first = ctx.onepass
-        ctx.onepass = False
-        dlogits = ctx.saved_tensors[4] if first else torch.empty_like(logits)
-        _core.ce_opts_bwd(logits.data_ptr(), t32.data_ptr(),
-                          row_lse.data_ptr(), dlogits.data_ptr(), g.data_ptr(),
-                          state.data_ptr(), R, V, stream=s, skip_if_unit=first,
-                          **ctx.opts)
-        return dlogits, None, None, None, None
+            _core.ce_opts_bwd(*ptrs, saved[0].data_ptr(), R, V, stream=s,
+                              skip_if_unit=first, **ctx.opts)
+        return dlogits, None, None
 
 
 def _check_options(ignore_index, label_smoothing, z_loss):
@@ -161,10 +133,13 @@ def fused_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, *,
     targets (R,).  Options and their edge cases: module docstring."""
     label_smoothing, z_loss = _check_options(ignore_index, label_smoothing,
                                              z_loss)
-    if ignore_index is None and label_smoothing == 0.0 and z_loss == 0.0:
-        return _FusedCEFn.apply(logits, targets)
-    return _FusedCEOptsFn.apply(logits, targets, ignore_index,
-                                label_smoothing, z_loss)
+    opts = None
+    if ignore_index is not None or label_smoothing != 0.0 or z_loss != 0.0:
+        has_ignore = ignore_index is not None
+        opts = dict(ignore_index=ignore_index if has_ignore else 0,
+                    has_ignore=has_ignore, label_smoothing=label_smoothing,
+                    z_loss=z_loss)
+    return _FusedCEFn.apply(logits, targets, opts)
 
 
 def cross_entropy_reference(logits_fp32: torch.Tensor, targets: torch.Tensor,

@@ -622,7 +622,7 @@ def bias_corrections(b1, b2, step):
 
 # ------------------------------------------------------ fused cross-entropy
 #
-# The kernels (csrc/ce_kernels.hip, ce_opts_kernels.hip, ce_common.h) evaluate
+# The kernels (csrc/ce_kernels.hip) evaluate
 # per row of bf16 logits, in fp32,
 #
 #   m    = max_j x_j                                   (exact)

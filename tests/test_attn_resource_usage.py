@@ -6,12 +6,7 @@ VGPRs, no AGPRs, no scratch, no spills, 32 KB of LDS, hence 4 waves/SIMD and
 4 workgroups of 4 waves per CU.  A spill would put scratch traffic into the
 tile loop; more registers or more LDS would take a workgroup off every CU.
 """
-import os
-import re
-import subprocess
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sharedtensor_amd", "csrc")
+from resource_report import kernel_resources
 
 LDS_PER_CU = 160 * 1024
 SIMDS_PER_CU = 4
@@ -19,35 +14,8 @@ WAVES_PER_BLOCK = 4     # 256 threads
 VGPR_FILE = 512         # unified VGPR + AGPR budget of one SIMD lane
 
 
-def _report(tmp_path):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cmd = [os.path.join(rocm, "bin", "hipcc"), "--offload-device-only", "-c",
-           os.path.join(CSRC, "attn_kernels.hip"), "-o",
-           str(tmp_path / "attn_dev.out"), "--offload-arch=gfx950",
-           "-std=c++20", "-O3", "-DSHAMD_WITH_HIP", "-DNDEBUG", f"-I{CSRC}",
-           f"-I{rocm}/include", "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    kernels, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"\s(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|"
-                      r"ScratchSize \[bytes/lane\]|"
-                      r"Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): "
-                      r"(\d+)", line)
-        if m and name:
-            key = m.group(1)
-            key = key if key.endswith("Spill") else key.split(" ")[0]
-            kernels[name][key] = int(m.group(2))
-    return kernels
-
-
 def test_attn_fwd_no_scratch_four_blocks_per_cu(tmp_path):
-    kernels = _report(tmp_path)
+    kernels = kernel_resources("attn_kernels.hip", tmp_path)
     (res,) = [v for k, v in kernels.items() if "k_attn_fwd_causal_hd64" in k]
     assert res["ScratchSize"] == 0, res
     assert res["VGPRs Spill"] == 0 and res["SGPRs Spill"] == 0, res

@@ -1,4 +1,4 @@
-"""The fused cross-entropy kernels (csrc/ce_kernels.hip, ce_opts_kernels.hip)
+"""The fused cross-entropy kernels (csrc/ce_kernels.hip, all row policies)
 through their raw bindings, against the fp64 reference and the derived bound
 of tests/kernel_bounds.py: dlogits within 1 bf16 ulp + slack element by
 element, per-row loss / row_lse within the fp32 slack, row_m exact.
@@ -32,13 +32,13 @@ Cases and the branches they reach:
   test_skip_if_unit_strided_rows
       R = 2053 > the capped grid (2048 blocks; 1024 with the 512 knob): rows
       past the first sweep go through r += gridDim.x of
-      k_ce_bwd<., true> and k_ce_opts_bwd<., true, EXTRA off | on>, ignored
+      k_ce_bwd<., true, plain | masked | masked + extra>, ignored
       rows among them; g = 2 within bound, g = 1 leaves the sentinel.
   test_options
       {ignore}, {eps}, {z}, {ignore, eps, z} x V in {13, 1003, 50257} over
-      k_ce_opts_fwd_grad, k_ce_opts_fwd and k_ce_opts_bwd (EXTRA off and
-      on); the three row kinds (valid, ignored, out of range); ignored rows
-      poisoned with NaN and 1e30 against zeros, bitwise.
+      k_ce_fwd_grad, k_ce_fwd and k_ce_bwd with the masked policies (EXTRA
+      off and on); the three row kinds (valid, ignored, out of range);
+      ignored rows poisoned with NaN and 1e30 against zeros, bitwise.
   test_scan_state
       k_ce_opts_scan counts and inv_count for R around its 1024 threads.
   test_row_isolation

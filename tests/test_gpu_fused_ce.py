@@ -32,6 +32,35 @@ def test_fwd_bwd_matches_torch(R, V):
                 targets, "fused_cross_entropy", f"R={R}/V={V}")
 
 
+def test_default_call_stays_off_the_option_path(monkeypatch):
+    """No option set: no scan of the targets (hence no state tensor), with
+    the gradient and under no_grad."""
+    def no_scan(*args, **kwargs):
+        raise AssertionError("the default call launched ce_opts_scan")
+    monkeypatch.setattr(fused_ce._core, "ce_opts_scan", no_scan)
+    torch.manual_seed(16)
+    R, V = 3, 13
+    logits = (torch.randn(R, V, device="cuda") * 3).to(torch.bfloat16)
+    targets = torch.randint(0, V, (R,), device="cuda")
+
+    lt = logits.clone().requires_grad_(True)
+    loss_t = torch.nn.functional.cross_entropy(lt.float(), targets)
+    loss_t.backward()
+
+    lf = logits.clone().requires_grad_(True)
+    loss_f = fused_ce.fused_cross_entropy(lf, targets)
+    loss_f.backward()
+    with torch.no_grad():
+        loss_n = fused_ce.fused_cross_entropy(logits, targets)
+    torch.cuda.synchronize()
+
+    for loss in (loss_f, loss_n):
+        torch.testing.assert_close(loss.float(), loss_t.float(), rtol=2e-3,
+                                   atol=2e-3)
+    torch.testing.assert_close(lf.grad.float(), lt.grad.float(), rtol=5e-2,
+                               atol=1e-4)
+
+
 def test_upstream_grad_scaling():
     torch.manual_seed(1)
     R, V = 32, 512

@@ -1,5 +1,5 @@
 """Fused cross-entropy with ignore_index, label smoothing and z-loss
-(csrc/ce_opts_kernels.hip) against cross_entropy_reference on the same bf16
+(csrc/ce_kernels.hip) against cross_entropy_reference on the same bf16
 logits upcast to fp32.
 
 Shapes and seam targets are those of test_gpu_fused_ce_onepass.py: every

@@ -7,39 +7,13 @@ ungrouped kernel with the same template arguments (compiled here the same
 way), and the 3 KB of LDS that stage one tile's segments (3 arrays of
 GROUP_TILE = 256 four-byte entries), far from limiting the blocks per CU.
 """
-import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sharedtensor_amd", "csrc")
+from resource_report import kernel_resources
+
 LDS_CAP = 3 * 256 * 4
-
-
-def _report(tmp_path, src):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cmd = [os.path.join(rocm, "bin", "hipcc"), "--offload-device-only", "-c",
-           os.path.join(CSRC, src), "-o", str(tmp_path / (src + ".out")),
-           "--offload-arch=gfx950", "-std=c++20", "-O3", "-DSHAMD_WITH_HIP",
-           "-DNDEBUG", f"-I{CSRC}", f"-I{rocm}/include",
-           "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    kernels, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"\s(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|"
-                      r"Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): "
-                      r"(\d+)", line)
-        if m and name:
-            kernels[name][m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
 
 
 def _key(mangled):
@@ -54,8 +28,8 @@ def _key(mangled):
 @pytest.fixture(scope="module")
 def reports(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("resource_usage")
-    return (_report(tmp, "optim_group_kernels.hip"),
-            _report(tmp, "hip_kernels.hip"))
+    return (kernel_resources("optim_group_kernels.hip", tmp),
+            kernel_resources("hip_kernels.hip", tmp))
 
 
 def test_grouped_kernels_no_scratch_same_occupancy_small_lds(reports):

@@ -7,12 +7,9 @@ or a private array in scratch would put memory traffic into the step loop;
 LDS beyond 160 KB would not launch.  The VGPR and occupancy figures found
 are printed as a record (profiles/r09/).
 """
-import os
 import re
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sharedtensor_amd", "csrc")
+from resource_report import kernel_resources
 
 LDS_PER_CU = 160 * 1024
 VGPR_FILE = 512
@@ -22,35 +19,8 @@ PANEL = 64 * 128 * 2    # one [64 tokens][128 features] bf16 panel
 BUILT = {(1, 1, 2): 2, (1, 1, 1): 3, (2, 1, 2): 2}
 
 
-def _report(tmp_path):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cmd = [os.path.join(rocm, "bin", "hipcc"), "--offload-device-only", "-c",
-           os.path.join(CSRC, "wgrad_kernels.hip"), "-o",
-           str(tmp_path / "wgrad_dev.out"), "--offload-arch=gfx950",
-           "-std=c++20", "-O3", "-DSHAMD_WITH_HIP", "-DNDEBUG", f"-I{CSRC}",
-           f"-I{rocm}/include", "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    kernels, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"\s(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|"
-                      r"ScratchSize \[bytes/lane\]|"
-                      r"Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): "
-                      r"(\d+)", line)
-        if m and name:
-            key = m.group(1)
-            key = key if key.endswith("Spill") else key.split(" ")[0]
-            kernels[name][key] = int(m.group(2))
-    return kernels
-
-
 def test_wgrad_kernels_no_scratch_lds_as_planned(tmp_path):
-    kernels = _report(tmp_path)
+    kernels = kernel_resources("wgrad_kernels.hip", tmp_path)
     found = {}
     for name, res in kernels.items():
         m = re.search(r"7k_wgradILi(\d)ELi(\d)ELi(\d)EE", name)
@@ -78,7 +48,7 @@ def test_wgrad_kernels_no_scratch_lds_as_planned(tmp_path):
 
 
 def test_reduce_kernel_is_small(tmp_path):
-    kernels = _report(tmp_path)
+    kernels = kernel_resources("wgrad_kernels.hip", tmp_path)
     (res,) = [v for k, v in kernels.items() if "k_wgrad_reduce" in k]
     assert res["ScratchSize"] == 0 and res["LDS"] == 0, res
     assert res["VGPRs Spill"] == 0 and res["SGPRs Spill"] == 0, res
