@@ -4,7 +4,8 @@ add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
 GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
 section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
 the fused bias-gradient section, `--only-attn` the attention forward,
-`--only-wgrad` the split-K weight-gradient kernel."""
+`--only-attn-bwd` the attention backward, `--only-wgrad` the split-K
+weight-gradient kernel."""
 import json
 import sys
 import time
@@ -222,6 +223,80 @@ def bench_attn(out, rounds=7, iters=20):
         out[n + "_tbps"] = round(byts / med / 1e9, 2)
 
 
+def bench_attn_bwd(out, rounds=7, iters=20):
+    # ---- causal attention backward at the same shape and layout: our two
+    # kernels (attn_backward) against the aten efficient-attention backward,
+    # both fed the out and lse of our forward.  Arms interleaved round by
+    # round, device-event timed; median and range over the rounds.  258 GFLOP
+    # (causal half of five B H T^2 D products) and 0.8 GB (q, k, v, out, dout
+    # read and dq, dk, dv written once) per call.
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from sharedtensor_amd.ops import fused_attn
+    B, H, T, D = 64, 12, 1024, 64
+    C = H * D
+    qkv = torch.randn(B, T, 3 * C, device="cuda").to(torch.bfloat16)
+    q, k, v = (x.view(B, T, H, D).transpose(1, 2)
+               for x in qkv.split(C, dim=2))
+    dout = torch.randn(B, T, H, D, device="cuda").to(
+        torch.bfloat16).transpose(1, 2)
+    o, lse = fused_attn.attn_forward(q, k, v)
+    o = o.transpose(1, 2)
+    assert fused_attn.can_use_backward(q, k, v, o, lse, dout)
+    grads = [torch.empty(B, T, H, D, dtype=torch.bfloat16,
+                         device="cuda").transpose(1, 2) for _ in range(3)]
+    delta = torch.empty(B, H, T, dtype=torch.float32, device="cuda")
+    seed, offset = fused_attn._philox_state()
+    pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
+           SDPBackend.MATH]
+    bwd = torch.ops.aten._scaled_dot_product_efficient_attention_backward
+
+    def aten():
+        with sdpa_kernel(pri, set_priority=True):
+            return bwd(dout, q, k, v, None, o, lse, seed, offset, 0.0,
+                       [True, True, True, False], True)
+
+    arms = {"aten_efficient_attn_bwd": aten,
+            "fused_attn_bwd": lambda: fused_attn.attn_backward(
+                q, k, v, o, lse, dout, None, *grads, delta=delta)}
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for fn in arms.values():
+        timed(fn)
+    ms = {n: [] for n in arms}
+    for _ in range(rounds):
+        for n, fn in arms.items():
+            ms[n].append(timed(fn))
+    flop = 10 * B * H * T * T * D / 2
+    byts = 8 * B * H * T * D * 2
+    out["attn_bwd_shape"] = dict(B=B, H=H, T=T, D=D, rounds=rounds,
+                                 iters=iters)
+    for n, xs in ms.items():
+        xs = sorted(xs)
+        med = xs[len(xs) // 2]
+        out[n + "_ms_median"] = round(med, 4)
+        out[n + "_ms_range"] = [round(xs[0], 4), round(xs[-1], 4)]
+        out[n + "_tflops"] = round(flop / med / 1e9, 1)
+        out[n + "_tbps"] = round(byts / med / 1e9, 2)
+    out["fused_median_below_aten_min"] = bool(
+        out["fused_attn_bwd_ms_median"]
+        < out["aten_efficient_attn_bwd_ms_range"][0])
+    # repeats of the fused arm are bit-identical
+    first = [g.clone() for g in grads]
+    arms["fused_attn_bwd"]()
+    torch.cuda.synchronize()
+    out["fused_repeat_bit_equal"] = all(
+        torch.equal(a, b) for a, b in zip(first, grads))
+
+
 def load_tunableop():
     """The checked-in TunableOp GEMM table, loaded as bench.py loads it."""
     import os
@@ -303,6 +378,10 @@ def main():
         return
     if "--only-attn" in sys.argv[1:]:
         bench_attn(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-attn-bwd" in sys.argv[1:]:
+        bench_attn_bwd(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-wgrad" in sys.argv[1:]:

@@ -1,0 +1,629 @@
+// Causal bf16 attention backward for head dim 64 (GPT-2), the counterpart of
+// attn_kernels.hip: fp32 accumulation, bf16 in and out, no dropout, no bias,
+// top-left aligned causal mask (Tq == Tk).  Two kernels, no atomics, one fp32
+// workspace delta (B, H, T); every output element is written once by one
+// lane from one fixed-order sum, so repeats are bit-identical.
+//
+// The softmax is not recomputed: with the forward's natural-log lse,
+//   P = exp2(s * scale * log2(e) - lse * log2(e)),
+//   dS = P * (dP - delta),  delta[q] = sum_d dO[q][d] O[q][d],
+//   dQ = scale dS K,  dK = scale dS^T Q,  dV = P^T dO.
+//
+// Plan (tests/test_attn_bwd_resource_usage.py holds both kernels to it):
+//   * Tiles in LDS are 64 rows x 128 B.  16-byte chunk c of row r sits at
+//     chunk c ^ f((r >> 1) & 7), f(x) = x ^ ((x & 1) << 2).  One swizzle
+//     serves both reads of a tile, so no tile is staged twice:
+//       - row-wise (ds_read_b128, 16 consecutive rows, one chunk): f is a
+//         bijection of 0..7, so the 16 lanes touch 16 different 16-byte
+//         slots of the 256-byte bank line, as the forward's K swizzle does;
+//       - transposed (ds_read_b64_tr_b16, a 32-lane half fetches 4 rows
+//         r0..r0+3 x 64 B, r0 a multiple of 4): rows r0, r0+1 get f = x and
+//         rows r0+2, r0+3 get f = x ^ 5, which moves their 64 bytes to the
+//         other half of the 128-byte row, so the 4 x 64 B cover the bank
+//         line once, as the forward's V swizzle does.
+//     This was chosen from the bank arithmetic; the counters then showed 4.1%
+//     (dq) and 4.6% (dkdv) of the LDS-active cycles as bank-conflict cycles,
+//     against 3.4% in the forward (profiles/r11/).  Staging K twice (48 KB,
+//     one workgroup per CU fewer in k_attn_bwd_dq) was not measured.
+//   * The lane layouts are the forward's.  mfma_32x32x16(A, B) with A read
+//     row-wise from LDS and B held in registers gives a lane one column
+//     (lane & 31) and the 16 rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+//     Registers 8s .. 8s+7 of such a result, converted to bf16, are the B
+//     operand of k-step s of a second mfma whose A operand is the transposed
+//     read of a tile: that read delivers the rows in the same permuted
+//     order, so P and dS never move between lanes or through LDS.
+//
+//   k_attn_bwd_dq: workgroup = 4 waves = 128 query rows of one (b, h), a
+//   lane owns one query; loops over 64-key tiles up to the diagonal.
+//   * Q and dO stay in registers (B operands).  delta comes from the lane's
+//     half rows of dO and O plus one exchange between the lane halves and is
+//     written to the workspace (no preprocess pass).
+//   * K and V tiles double-buffered in LDS, 2 x (8 KB + 8 KB) = 32 KB, next
+//     tile's global loads issued before the MFMAs, one barrier per tile.
+//   * per 32-key half tile: S^T = mfma(K, Q), dP^T = mfma(V, dO) (V read
+//     row-wise like K), dS^T = P^T (dP^T - delta) per lane,
+//     dQ^T += mfma(K^T, dS^T).  Working on half tiles keeps S^T and dP^T at
+//     16 registers each; half tiles wholly above a wave's rows are skipped,
+//     only the tile that crosses the diagonal is masked.
+//   * scale is applied once to dQ in the epilogue; dQ goes through LDS so
+//     that every global store is a whole 128-byte row.
+//   * Grid: the forward's (query blocks of one (b, h) consecutive on one
+//     XCD, heaviest (last) block first).
+//   * Resources: amdgpu_waves_per_eu(3, 3): at most 160 VGPRs (154 as
+//     built; 168 is the limit of the occupancy step), no AGPRs, no scratch,
+//     no spills, 32 KB of LDS -> 3 waves/SIMD, 3 workgroups per CU.
+//     Q, dO, dQ^T, S^T, dP^T, dS^T and the 16 staging registers are 136
+//     before any address; held to 128 registers (4 waves/SIMD) the compiler
+//     spills 38 of them into the tile loop.
+//
+//   k_attn_bwd_dkdv: workgroup = 4 waves = 128 keys of one (b, h), a lane
+//   owns one key; loops over 64-query tiles from the diagonal tile to the end.
+//   * K and V stay in registers (B operands); dK^T and dV^T are 64 fp32
+//     accumulator registers per lane.
+//   * Q and dO tiles plus 64 (-lse log2 e) and 64 delta values are
+//     double-buffered in LDS: 2 x (8 KB + 8 KB + 512 B) = 33 KB.
+//   * per 32-query half tile: S = mfma(Q, K), dP = mfma(dO, V); P and dS per
+//     register, lse and delta of the register's query read from LDS as
+//     16-byte broadcast reads; dV^T += mfma(dO^T, P), dK^T += mfma(Q^T, dS).
+//   * Half tiles wholly before a wave's keys are skipped, only the tile that
+//     crosses the diagonal is masked, queries at or past T contribute zero
+//     (their Q, dO, lse and delta are staged as zeros).
+//   * dK is scaled in the epilogue; dK and dV go through LDS to whole-row
+//     stores.
+//   * Grid: key blocks of one (b, h) consecutive on one XCD, first
+//     (heaviest) key block first.
+//   * Resources: K, V, the accumulators, S, dP and the staging registers do
+//     not fit 128 registers.  amdgpu_waves_per_eu(2, 2): at most 200 VGPRs
+//     (198 as built; 256 is the limit of the occupancy step), no AGPRs, no
+//     scratch, no spills -> 2 waves/SIMD, 2 workgroups per CU (LDS would
+//     allow 4).
+//
+// Every T is bounds-checked: rows at or past T are read as zeros (never from
+// memory) and never stored.
+#include <hip/hip_runtime.h>
+
+#include "device_util.h"
+#include "hip_api.h"
+
+namespace shamd {
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kD = 64;          // head dim
+constexpr int kRW = 32;         // rows (queries or keys) per wave
+constexpr int kWaves = 4;
+constexpr int kRB = kRW * kWaves;  // rows per workgroup
+constexpr int kTile = 64;       // rows per LDS tile
+constexpr int kTileBytes = kTile * kD * 2;
+constexpr int kXcd = 8;
+constexpr float kLog2e = 1.4426950408889634f;
+
+struct BwdStrides {
+  int64_t b, t, h;  // elements
+};
+
+// the chunk swizzle of a row: f((row >> 1) & 7)
+__device__ __forceinline__ int swz(int row) {
+  int x = (row >> 1) & 7;
+  return x ^ ((x & 1) << 2);
+}
+// byte offset of 16-byte chunk `ch` (0..7) of row `row` in a tile
+__device__ __forceinline__ int t_off(int row, int ch) {
+  return row * 128 + ((ch ^ swz(row)) << 4);
+}
+
+__device__ __forceinline__ u32x4 load16_or_zero(const uint16_t* p, bool ok) {
+  u32x4 z = {0, 0, 0, 0};
+  return ok ? *reinterpret_cast<const u32x4*>(p) : z;
+}
+
+// the other lane half's value (lane ^ 32)
+__device__ __forceinline__ float other_half(float x, int lane) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2,
+                                          __builtin_bit_cast(int, x)));
+}
+
+// Per-lane parts of the two LDS read patterns.
+struct LaneOffs {
+  // row-wise A operand: row 32 blk + r, chunk 2 ks + hi -> row_ks[ks] +
+  // 32 * 128 * blk (the swizzle depends on r alone)
+  int row_ks[4];
+  // transposed A operand: tr[p] is the lane's address for rows 0..3 + 4 hi
+  // of a 16-row group and a column block nb with nb ^ jj == p (jj: second
+  // 8 rows of the group, which flips bit 2 of the swizzle)
+  int tr[2];
+};
+
+__device__ __forceinline__ LaneOffs lane_offs(int lane) {
+  LaneOffs o;
+  const int r = lane & 31, hi = lane >> 5;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) o.row_ks[ks] = t_off(r, 2 * ks + hi);
+  // 16-lane group g reads rows 4 (g >> 1) + 0..3, columns 16 (g & 1) + 0..15
+  // of the 32-column block; lane 4 qq + p of the group supplies row qq,
+  // columns 4 p .. 4 p + 3
+  const int grp = lane >> 4, gi = lane & 15;
+  const int tq = gi >> 2, tp = gi & 3;
+  const int row = 4 * (grp >> 1) + tq;
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+    o.tr[p] = t_off(row, 4 * p + 2 * (grp & 1) + (tp >> 1)) + 8 * (tp & 1);
+  return o;
+}
+
+// A operand read row-wise: lane holds tile[32 blk + r][16 ks + 8 hi + j]
+__device__ __forceinline__ bf16x8 row_frag(const unsigned char* tile,
+                                           const LaneOffs& lo, int blk,
+                                           int ks) {
+  u32x4 t = *reinterpret_cast<const u32x4*>(tile + blk * (kRW * 128) +
+                                            lo.row_ks[ks]);
+  return __builtin_bit_cast(bf16x8, t);
+}
+
+// A operand read transposed: lane holds, as element j,
+// tile[16 ss + 8 (j >> 2) + 4 hi + (j & 3)][32 nb + r], the row order the
+// registers 8 (ss & 1) .. + 7 of a 32 x 32 mfma result have
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile,
+                                          const LaneOffs& lo, int ss, int nb) {
+  bf16x8 f;
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj) {
+    // rows 16 ss + 8 jj + ..: (row >> 1) & 7 gains 4 jj, the swizzle flips
+    // bit 2 of the chunk with jj, as nb does
+    auto* a = reinterpret_cast<__attribute__((address_space(3))) s16x4*>(
+        (uintptr_t)(tile + (16 * ss + 8 * jj) * 128 + lo.tr[nb ^ jj]));
+    s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a);
+    bf16x4 tb = __builtin_bit_cast(bf16x4, tr);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[4 * jj + e] = tb[e];
+  }
+  return f;
+}
+
+// blockIdx -> (batch*head, block slot): block ids round-robin over the XCDs,
+// the blocks of one (b, h) consecutive on one XCD
+__device__ __forceinline__ bool grid_map(int nbh, int nblk, int& bh,
+                                         int& slot_in_bh) {
+  const int xcd = blockIdx.x % kXcd;
+  const int slot = blockIdx.x / kXcd;
+  bh = (slot / nblk) * kXcd + xcd;
+  slot_in_bh = slot % nblk;
+  return bh < nbh;
+}
+
+// fp32 rows of a wave -> bf16 through the wave's 4 KB of LDS -> whole-row
+// global stores.  acc: lane holds row r, columns 32 nb + (reg & 3) +
+// 8 (reg >> 2) + 4 hi.
+__device__ __forceinline__ void stage_rows(unsigned char* Ow,
+                                           const f32x16 (&acc)[2], float mul,
+                                           int r, int hi) {
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[e] = (__bf16)(acc[nb][4 * g + e] * mul);
+      // d = 32 nb + 8 g + 4 hi + e: chunk 4 nb + g, its half hi
+      *reinterpret_cast<bf16x4*>(Ow + t_off(r, 4 * nb + g) + 8 * hi) = f;
+    }
+}
+
+__device__ __forceinline__ void store_rows(const unsigned char* Ow,
+                                           uint16_t* dst, int64_t row_stride,
+                                           int row0, int T, int lane) {
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    int row = pass * 8 + (lane >> 3), ch = lane & 7;
+    u32x4 val = *reinterpret_cast<const u32x4*>(Ow + t_off(row, ch));
+    int gr = row0 + row;
+    if (gr < T)
+      *reinterpret_cast<u32x4*>(dst + (int64_t)gr * row_stride + 8 * ch) = val;
+  }
+}
+
+// ------------------------------------------------------------------ dQ
+
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(3, 3))) void k_attn_bwd_dq(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+    const uint16_t* __restrict__ v, const uint16_t* __restrict__ out,
+    const uint16_t* __restrict__ dout, const float* __restrict__ lse,
+    uint16_t* __restrict__ dq, float* __restrict__ delta, int nbh, int H,
+    int T, int nqb, BwdStrides sq, BwdStrides sk, BwdStrides sv, BwdStrides so,
+    BwdStrides sdo, BwdStrides sdq, int64_t lse_stride, float scale) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * kTileBytes];
+  // K buffers at 0 and kTileBytes, V buffers behind them
+  unsigned char* const ldsK = lds;
+  unsigned char* const ldsV = lds + 2 * kTileBytes;
+
+  int bh, slot;
+  if (!grid_map(nbh, nqb, bh, slot)) return;  // whole workgroup
+  const int qb = nqb - 1 - slot;              // heaviest block first
+  const int b = bh / H, h = bh % H;
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int r = lane & 31, hi = lane >> 5;
+  const LaneOffs lo = lane_offs(lane);
+
+  const int q0 = qb * kRB;
+  const int qw0 = q0 + wave * kRW;  // the wave's first query row
+  const int qrow = qw0 + r;         // this lane's query row
+  const bool qok = qrow < T;
+
+  const uint16_t* qp = q + b * sq.b + h * sq.h + (int64_t)qrow * sq.t;
+  const uint16_t* op = out + b * so.b + h * so.h + (int64_t)qrow * so.t;
+  const uint16_t* dop = dout + b * sdo.b + h * sdo.h + (int64_t)qrow * sdo.t;
+  const uint16_t* kp = k + b * sk.b + h * sk.h;
+  const uint16_t* vp = v + b * sv.b + h * sv.h;
+
+  // Q and dO fragments: B operands; lane holds X[qrow][16 ks + 8 hi + j].
+  // delta from the same elements of dO and O.
+  bf16x8 qf[4], dof[4];
+  float dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int d0 = 16 * ks + 8 * hi;
+    qf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(qp + d0, qok));
+    dof[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(dop + d0, qok));
+    bf16x8 of = __builtin_bit_cast(bf16x8, load16_or_zero(op + d0, qok));
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      dl = __builtin_fmaf((float)dof[ks][e], (float)of[e], dl);
+  }
+  dl += other_half(dl, lane);
+  if (hi == 0 && qok) delta[(int64_t)bh * T + qrow] = dl;
+  // -lse * log2(e); rows past T: any finite value, their dS is 0 * finite
+  const float nl = qok ? -lse[(int64_t)bh * lse_stride + qrow] * kLog2e : 0.f;
+  const float scale_log2e = scale * kLog2e;
+
+  // staging: thread covers 16-byte chunk (tid & 7) of keys (tid >> 3) and
+  // (tid >> 3) + 32 of the tile, for K and for V
+  const int skey = tid >> 3, sch = tid & 7;
+  u32x4 stK[2], stV[2];
+  auto issue = [&](int kv0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int key = kv0 + skey + 32 * i;
+      bool ok = key < T;
+      stK[i] = load16_or_zero(kp + (int64_t)key * sk.t + 8 * sch, ok);
+      stV[i] = load16_or_zero(vp + (int64_t)key * sv.t + 8 * sch, ok);
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int off = buf * kTileBytes + t_off(skey + 32 * i, sch);
+      *reinterpret_cast<u32x4*>(ldsK + off) = stK[i];
+      *reinterpret_cast<u32x4*>(ldsV + off) = stV[i];
+    }
+  };
+
+  const int kv_end = min(T, q0 + kRB);             // keys this block can see
+  const int ntiles = (kv_end + kTile - 1) / kTile;  // >= 1
+
+  f32x16 acc[2];  // dQ^T: lane holds dQ[qrow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
+
+  issue(0);
+  commit(0);
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int cur = t & 1;
+    const int kv0 = t * kTile;
+    const bool more = t + 1 < ntiles;
+    if (more) issue(kv0 + kTile);
+
+    const unsigned char* Kt = ldsK + cur * kTileBytes;
+    const unsigned char* Vt = ldsV + cur * kTileBytes;
+    // keys of the tile are kv0 + 4 hi + c, c a register constant; key c is
+    // visible when c <= vis.  Tiles below the diagonal: everything.
+    const int vis = kv0 + kTile - 1 > qw0 ? qrow - kv0 - 4 * hi : kTile;
+
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      // wave-uniform: the half tile has keys the wave's rows can see
+      if (kv0 + 32 * kb > qw0 + kRW - 1) continue;
+
+      // S^T = K Q^T and dP^T = V dO^T for keys kv0 + 32 kb + keymap(reg, hi)
+      f32x16 s, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Kt, lo, kb, ks),
+                                                    qf[ks], s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vt, lo, kb, ks),
+                                                     dof[ks], dp, 0, 0, 0);
+      }
+
+      bf16x8 dsf[2];  // dS^T fragments: k-steps 2 kb and 2 kb + 1
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float p = __builtin_amdgcn_exp2f(
+            __builtin_fmaf(s[i], scale_log2e, nl));
+        if (32 * kb + (i & 3) + 8 * (i >> 2) > vis) p = 0.f;
+        dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl));
+      }
+
+      // dQ^T += K^T dS^T
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+          acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(Kt, lo, 2 * kb + h2, nb), dsf[h2], acc[nb], 0, 0, 0);
+    }
+
+    if (more) commit(cur ^ 1);
+    __syncthreads();
+  }
+
+  // the loop's last barrier is behind every wave: the tiles are dead
+  unsigned char* const Ow = lds + wave * (kRW * 128);
+  stage_rows(Ow, acc, scale, r, hi);
+  __syncthreads();
+  store_rows(Ow, dq + b * sdq.b + h * sdq.h, sdq.t, qw0, T, lane);
+}
+
+// ------------------------------------------------------------- dK, dV
+
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(2, 2))) void k_attn_bwd_dkdv(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+    const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int nbh, int H,
+    int T, int nkb, BwdStrides sq, BwdStrides sk, BwdStrides sv,
+    BwdStrides sdo, BwdStrides sdk, BwdStrides sdv, int64_t lse_stride,
+    float scale) {
+  __shared__ __attribute__((aligned(16))) unsigned char
+      lds[4 * kTileBytes + 2 * 2 * kTile * 4];
+  // Q buffers at 0 and kTileBytes, dO buffers behind them, then per buffer
+  // 64 floats of -lse log2(e) and 64 of delta
+  unsigned char* const ldsQ = lds;
+  unsigned char* const ldsD = lds + 2 * kTileBytes;
+  float* const ldsLD = reinterpret_cast<float*>(lds + 4 * kTileBytes);
+
+  int bh, kblk;
+  if (!grid_map(nbh, nkb, bh, kblk)) return;  // whole workgroup
+  const int b = bh / H, h = bh % H;           // first key block first
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int r = lane & 31, hi = lane >> 5;
+  const LaneOffs lo = lane_offs(lane);
+
+  const int k0 = kblk * kRB;
+  const int kw0 = k0 + wave * kRW;  // the wave's first key
+  const int krow = kw0 + r;         // this lane's key
+  const bool kok = krow < T;
+
+  const uint16_t* kp = k + b * sk.b + h * sk.h + (int64_t)krow * sk.t;
+  const uint16_t* vp = v + b * sv.b + h * sv.h + (int64_t)krow * sv.t;
+  const uint16_t* qp = q + b * sq.b + h * sq.h;
+  const uint16_t* dop = dout + b * sdo.b + h * sdo.h;
+  const float* lsep = lse + (int64_t)bh * lse_stride;
+  const float* deltap = delta + (int64_t)bh * T;
+
+  // K and V fragments: B operands; lane holds X[krow][16 ks + 8 hi + j]
+  bf16x8 kf[4], vf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int d0 = 16 * ks + 8 * hi;
+    kf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(kp + d0, kok));
+    vf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(vp + d0, kok));
+  }
+  const float scale_log2e = scale * kLog2e;
+
+  // staging: thread covers 16-byte chunk (tid & 7) of queries (tid >> 3) and
+  // (tid >> 3) + 32 of the tile, for Q and for dO; threads 0..63 one lse,
+  // threads 64..127 one delta
+  const int srow = tid >> 3, sch = tid & 7;
+  u32x4 stQ[2], stD[2];
+  float stL = 0.f;
+  auto issue = [&](int qt0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int row = qt0 + srow + 32 * i;
+      bool ok = row < T;
+      stQ[i] = load16_or_zero(qp + (int64_t)row * sq.t + 8 * sch, ok);
+      stD[i] = load16_or_zero(dop + (int64_t)row * sdo.t + 8 * sch, ok);
+    }
+    if (tid < 2 * kTile) {
+      int row = qt0 + (tid & (kTile - 1));
+      stL = 0.f;
+      if (row < T) stL = tid < kTile ? -lsep[row] * kLog2e : deltap[row];
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int off = buf * kTileBytes + t_off(srow + 32 * i, sch);
+      *reinterpret_cast<u32x4*>(ldsQ + off) = stQ[i];
+      *reinterpret_cast<u32x4*>(ldsD + off) = stD[i];
+    }
+    if (tid < 2 * kTile) ldsLD[buf * 2 * kTile + tid] = stL;
+  };
+
+  const int t_begin = k0 / kTile;               // the tile of the block's keys
+  const int t_end = (T + kTile - 1) / kTile;    // > t_begin: k0 < T
+
+  // dK^T, dV^T: lane holds dX[krow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
+  f32x16 dka[2], dva[2];
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dka[nb][i] = dva[nb][i] = 0.f;
+
+  issue(t_begin * kTile);
+  commit(0);
+  __syncthreads();
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int cur = (t - t_begin) & 1;
+    const int qt0 = t * kTile;
+    const bool more = t + 1 < t_end;
+    if (more) issue(qt0 + kTile);
+
+    const unsigned char* Qt = ldsQ + cur * kTileBytes;
+    const unsigned char* Dt = ldsD + cur * kTileBytes;
+    const float* LD = ldsLD + cur * 2 * kTile;
+    // queries of the tile are qt0 + 4 hi + c, c a register constant; query c
+    // sees the lane's key when c >= need.  Tiles past the diagonal: all do.
+    const int need = qt0 < kw0 + kRW - 1 ? krow - qt0 - 4 * hi : 0;
+
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh) {
+      // wave-uniform: the half tile has queries that see the wave's keys
+      if (qt0 + 32 * qh + 31 < kw0) continue;
+
+      // S = Q K^T and dP = dO V^T for queries qt0 + 32 qh + rowmap(reg, hi)
+      f32x16 s, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qt, lo, qh, ks),
+                                                    kf[ks], s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Dt, lo, qh, ks),
+                                                     vf[ks], dp, 0, 0, 0);
+      }
+
+      bf16x8 pf[2], dsf[2];  // P and dS fragments: k-steps 2 qh and 2 qh + 1
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        // registers 4 g .. 4 g + 3 are queries 32 qh + 8 g + 4 hi + 0..3
+        const int c0 = 32 * qh + 8 * g;
+        f32x4 nl4 = *reinterpret_cast<const f32x4*>(LD + c0 + 4 * hi);
+        f32x4 dl4 = *reinterpret_cast<const f32x4*>(LD + kTile + c0 + 4 * hi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = 4 * g + e;
+          float p = __builtin_amdgcn_exp2f(
+              __builtin_fmaf(s[i], scale_log2e, nl4[e]));
+          if (c0 + e < need) p = 0.f;
+          pf[i >> 3][i & 7] = (__bf16)p;
+          dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl4[e]));
+        }
+      }
+
+      // dV^T += dO^T P, dK^T += Q^T dS
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          dva[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(Dt, lo, 2 * qh + h2, nb), pf[h2], dva[nb], 0, 0, 0);
+          dka[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(Qt, lo, 2 * qh + h2, nb), dsf[h2], dka[nb], 0, 0, 0);
+        }
+    }
+
+    if (more) commit(cur ^ 1);
+    __syncthreads();
+  }
+
+  // the loop's last barrier is behind every wave: the tiles are dead; a wave
+  // owns 8 KB, dK rows in the first 4 KB and dV rows in the second
+  unsigned char* const Ow = lds + wave * (2 * kRW * 128);
+  stage_rows(Ow, dka, scale, r, hi);
+  stage_rows(Ow + kRW * 128, dva, 1.f, r, hi);
+  __syncthreads();
+  store_rows(Ow, dk + b * sdk.b + h * sdk.h, sdk.t, kw0, T, lane);
+  store_rows(Ow + kRW * 128, dv + b * sdv.b + h * sdv.h, sdv.t, kw0, T, lane);
+}
+
+}  // namespace
+
+void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
+                              const void* out, const void* dout,
+                              const float* lse, void* dq, void* dk, void* dv,
+                              float* delta, int64_t B, int64_t H, int64_t T,
+                              const int64_t* qs, const int64_t* ks,
+                              const int64_t* vs, const int64_t* os,
+                              const int64_t* dos, const int64_t* dqs,
+                              const int64_t* dks, const int64_t* dvs,
+                              int64_t lse_stride, float scale, hipStream_t s) {
+  const char* op = "attn_bwd_causal_hd64";
+  if (B <= 0 || H <= 0 || T <= 0)
+    throw std::runtime_error(std::string(op) + ": empty problem");
+  if (!(scale > 0.f) || scale > 3.0e38f)
+    throw std::runtime_error(std::string(op) + ": scale must be positive");
+  if (lse_stride < T)
+    throw std::runtime_error(std::string(op) + ": lse row shorter than T");
+  const void* ptrs[] = {q, k, v, out, dout, dq, dk, dv};
+  const char* names[] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
+  for (int i = 0; i < 8; ++i) {
+    if (!ptrs[i])
+      throw std::runtime_error(std::string(op) + ": " + names[i] + " is null");
+    check_align(ptrs[i], 16, op, names[i]);
+  }
+  if (!lse || !delta)
+    throw std::runtime_error(std::string(op) + ": lse or delta is null");
+  check_align(lse, 4, op, "lse");
+  check_align(delta, 4, op, "delta");
+  for (const int64_t* st : {qs, ks, vs, os, dos, dqs, dks, dvs})
+    for (int i = 0; i < 3; ++i)
+      if (st[i] < 0 || st[i] % 8)
+        throw std::runtime_error(std::string(op) +
+                                 ": strides must be multiples of 8 elements");
+  // no two output rows may overlap: with the dimensions of more than one
+  // element ordered by stride, the smallest stride covers a 64-element row
+  // and every further one the whole extent of the dimension before it
+  const int64_t dims[3] = {B, T, H};
+  for (const int64_t* st : {dqs, dks, dvs}) {
+    int64_t sd[3][2];
+    int n = 0;
+    for (int i = 0; i < 3; ++i)
+      if (dims[i] > 1) {
+        int j = n++;
+        for (; j > 0 && sd[j - 1][0] > st[i]; --j) {
+          sd[j][0] = sd[j - 1][0];
+          sd[j][1] = sd[j - 1][1];
+        }
+        sd[j][0] = st[i];
+        sd[j][1] = dims[i];
+      }
+    int64_t need = kD;
+    for (int i = 0; i < n; ++i) {
+      if (sd[i][0] < need)
+        throw std::runtime_error(std::string(op) +
+                                 ": output rows would overlap");
+      need = sd[i][0] * sd[i][1];
+    }
+  }
+  const int64_t nblk = (T + kRB - 1) / kRB;
+  const int64_t nbh = B * H;
+  const int64_t grid = (nbh + kXcd - 1) / kXcd * kXcd * nblk;
+  if (grid > 0x7fffffff || T > (1 << 30) || nbh > 0x7fffffff)
+    throw std::runtime_error(std::string(op) + ": problem too large");
+  auto st3 = [](const int64_t* p) { return BwdStrides{p[0], p[1], p[2]}; };
+  auto u16 = [](const void* p) { return static_cast<const uint16_t*>(p); };
+  k_attn_bwd_dq<<<dim3((unsigned)grid), dim3(256), 0, s>>>(
+      u16(q), u16(k), u16(v), u16(out), u16(dout), lse,
+      static_cast<uint16_t*>(dq), delta, (int)nbh, (int)H, (int)T, (int)nblk,
+      st3(qs), st3(ks), st3(vs), st3(os), st3(dos), st3(dqs), lse_stride,
+      scale);
+  HIP_CHECK(hipGetLastError());
+  k_attn_bwd_dkdv<<<dim3((unsigned)grid), dim3(256), 0, s>>>(
+      u16(q), u16(k), u16(v), u16(dout), lse, delta,
+      static_cast<uint16_t*>(dk), static_cast<uint16_t*>(dv), (int)nbh, (int)H,
+      (int)T, (int)nblk, st3(qs), st3(ks), st3(vs), st3(dos), st3(dks),
+      st3(dvs), lse_stride, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace shamd

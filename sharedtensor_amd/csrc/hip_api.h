@@ -336,6 +336,29 @@ void hip_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
                               const int64_t* v_strides, int64_t lse_stride,
                               float scale, hipStream_t s);
 
+// Causal bf16 attention backward, head dim 64 (attn_bwd_kernels.hip): two
+// kernels, no atomics, bit-identical across repeats.  q, k, v, out, dout are
+// read and dq, dk, dv written in place through element strides {batch,
+// token, head} (each a multiple of 8, pointers 16-byte aligned, the 64
+// elements of a head contiguous; output rows must not overlap).  `out` and
+// `lse` (B, H, lse_stride >= T, natural log) are the forward's.  `delta`
+// (B, H, T) fp32 is the only workspace: the first kernel fills it with
+// sum_d dout * out, the second reads it.  scale > 0.  Throws on anything
+// else.
+void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
+                              const void* out, const void* dout,
+                              const float* lse, void* dq, void* dk, void* dv,
+                              float* delta, int64_t B, int64_t H, int64_t T,
+                              const int64_t* q_strides,
+                              const int64_t* k_strides,
+                              const int64_t* v_strides,
+                              const int64_t* out_strides,
+                              const int64_t* dout_strides,
+                              const int64_t* dq_strides,
+                              const int64_t* dk_strides,
+                              const int64_t* dv_strides, int64_t lse_stride,
+                              float scale, hipStream_t s);
+
 // Split-K bf16 weight gradient dW[N, K] = dY[M, N]^T X[M, K]
 // (wgrad_kernels.hip), fp32 accumulation.  ldy, ldx, ldw are row strides in
 // elements (multiples of 8, pointers 16-byte aligned).  `variant` picks the

@@ -64,10 +64,21 @@ FUSE_FC_BIAS_GRAD = False
 
 # Run the attention forward in our own kernel (ops/fused_attn.py: bf16, head
 # dim 64, causal) instead of the SDPA efficient-attention forward; the
-# backward stays the aten one, fed with our out and lse.  Numbers in
-# profiles/r08/.  SHTENS_FUSED_ATTN = 0 or 1 overrides the flag for an A/B
-# run; inputs the kernel does not take keep the SDPA path.
+# backward is chosen by FUSE_ATTN_BWD below.  Numbers in profiles/r08/.
+# SHTENS_FUSED_ATTN = 0 or 1 overrides the flag for an A/B run; inputs the
+# kernel does not take keep the SDPA path.
 FUSE_ATTN_FWD = True
+
+# Run the attention backward in our own two kernels as well
+# (fused_attn.attn_backward) instead of the aten efficient-attention
+# backward: no atomics, bit-identical across repeats, no pre or post pass.
+# Measured 0.659 ms (0.656-0.661) against 0.773 ms (0.770-0.776) for the aten
+# call at B=64 H=12 T=1024, and 74.80 / 74.59 / 74.82 ms per bench.py step
+# against 75.89 / 76.01 / 75.95 for the parent, so it is on.  Numbers in
+# profiles/r11/.
+# SHTENS_FUSED_ATTN_BWD = 0 or 1 overrides the flag for an A/B run; it only
+# matters where the forward above is ours.
+FUSE_ATTN_BWD = True
 
 # Take the weight gradient of the four layer Linears (attn.qkv, attn.proj,
 # mlp.fc, mlp.proj) from our split-K kernel (ops/fused_wgrad.py) instead of
@@ -189,7 +200,9 @@ class CausalSelfAttention(nn.Module):
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         if _attn_ok(q, k, v):
             from ..ops import fused_attn
-            y = fused_attn.fused_causal_attention(q, k, v)
+            y = fused_attn.fused_causal_attention(
+                q, k, v, fused_backward=_flag("SHTENS_FUSED_ATTN_BWD",
+                                              FUSE_ATTN_BWD))
         elif x.is_cuda:
             # CK efficient-attention measured +16% end-to-end over the
             # default aotriton flash backend on MI355X at these shapes

@@ -1,14 +1,16 @@
 """Causal bf16 attention for head dim 64 with a hand-written forward kernel
-(csrc/attn_kernels.hip).
+(csrc/attn_kernels.hip) and a hand-written backward (csrc/attn_bwd_kernels.hip).
 
 ``fused_causal_attention(q, k, v)`` takes the (B, H, T, 64) views the model
 builds from the packed qkv GEMM output and reads them in place through their
 strides.  The forward writes ``out`` as contiguous (B, T, H, 64), returned as
 its (B, H, T, 64) view, the layout the aten efficient-attention op returns,
 so ``transpose(1, 2).contiguous()`` in the model stays a no-op, and ``lse``
-(B, H, T) fp32, the natural log of the softmax denominator.  The backward is
-the aten efficient-attention backward autograd runs on the SDPA path, fed
-with our ``out`` and ``lse``: the backward kernels do not change.
+(B, H, T) fp32, the natural log of the softmax denominator.  By default the
+backward is the aten efficient-attention backward autograd runs on the SDPA
+path, fed with our ``out`` and ``lse``.  With ``fused_backward=True`` it is
+``attn_backward``: two HIP kernels, no atomics, bit-identical across repeats,
+reading q, k, v, out and dout in place.
 
 ``can_use`` says whether the kernel takes the inputs; callers keep the SDPA
 path for everything else.  A call that passes ``can_use`` and then fails is
@@ -77,15 +79,77 @@ def attn_forward(q, k, v, scale=None, out=None, lse=None):
             or lse.dtype != torch.float32):
         raise ValueError("fused_attn: lse must be contiguous (B, H, T) fp32")
 
-    def bth(t):  # (batch, token, head) element strides of a (B, H, T, D) view
-        sb, sh, st, _ = t.stride()
-        return [sb, st, sh]
-
     s = torch.cuda.current_stream(q.device).cuda_stream
     _core.attn_fwd_causal_hd64(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                                out.data_ptr(), lse.data_ptr(), B, H, T,
-                               bth(q), bth(k), bth(v), T, float(scale), s)
+                               _bth(q), _bth(k), _bth(v), T, float(scale), s)
     return out, lse
+
+
+def can_use_backward(q, k, v, out, lse, dout) -> bool:
+    """``can_use`` for the backward: q, k, v as there; out and dout bf16
+    (B, H, T, 64) views under the same stride rules; lse contiguous (B, H, T)
+    fp32."""
+    if not can_use(q, k, v):
+        return False
+    for t in (out, dout):
+        if not (t.is_cuda and t.dtype == torch.bfloat16
+                and t.shape == q.shape and _strides_ok(t)):
+            return False
+    return (lse.is_cuda and lse.dtype == torch.float32
+            and lse.shape == q.shape[:3] and lse.is_contiguous())
+
+
+def _bth(t):
+    """(batch, token, head) element strides of a (B, H, T, D) view."""
+    sb, sh, st, _ = t.stride()
+    return [sb, st, sh]
+
+
+def attn_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
+                  dv=None, delta=None):
+    """dq, dk, dv of ``attn_forward`` on the current stream, as (B, H, T, 64)
+    views of contiguous (B, T, H, 64) bf16 buffers.  q, k, v, out, dout:
+    (B, H, T, 64) views; out and lse are the forward's.  A dout the kernel
+    cannot read in place (a stride rule) is made contiguous once; anything
+    else outside ``can_use_backward`` raises.  ``dq``/``dk``/``dv``
+    ((B, H, T, 64) views to write into) and the fp32 (B, H, T) workspace
+    ``delta`` may be passed in (tests put guard regions around them)."""
+    if (torch.is_tensor(dout) and dout.is_cuda and q.dim() == 4
+            and dout.dtype == torch.bfloat16 and dout.shape == q.shape
+            and not _strides_ok(dout)):
+        dout = dout.contiguous()
+    if not can_use_backward(q, k, v, out, lse, dout):
+        raise ValueError("fused_attn: inputs the backward kernels do not take "
+                         "(see can_use_backward)")
+    B, H, T, D = q.shape
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    grads = []
+    for g in (dq, dk, dv):
+        if g is None:
+            g = torch.empty((B, T, H, D), dtype=q.dtype,
+                            device=q.device).transpose(1, 2)
+        if (g.shape != q.shape or g.dtype != torch.bfloat16
+                or g.device != q.device or not _strides_ok(g)
+                or min(g.stride()[:3]) < D):
+            raise ValueError("fused_attn: dq, dk, dv must be bf16 "
+                             "(B, H, T, 64) views the kernel can write")
+        grads.append(g)
+    if delta is None:
+        delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    if (delta.shape != (B, H, T) or not delta.is_contiguous()
+            or delta.dtype != torch.float32 or delta.device != q.device):
+        raise ValueError("fused_attn: delta must be contiguous (B, H, T) fp32")
+    dq, dk, dv = grads
+    s = torch.cuda.current_stream(q.device).cuda_stream
+    _core.attn_bwd_causal_hd64(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+        dv.data_ptr(), delta.data_ptr(), B, H, T, _bth(q), _bth(k), _bth(v),
+        _bth(out), _bth(dout), _bth(dq), _bth(dk), _bth(dv), T, float(scale),
+        s)
+    return dq, dk, dv
 
 
 # dropout is 0, so the backward never reads the philox state; the aten
@@ -104,28 +168,34 @@ def _philox_state():
 
 class _FusedCausalAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, fused_backward):
         out, lse = attn_forward(q, k, v, scale)
         out = out.transpose(1, 2)  # (B, H, T, D) view, as aten returns it
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.scale = scale
+        ctx.fused_backward = fused_backward
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
+        if ctx.fused_backward:
+            dq, dk, dv = attn_backward(q, k, v, out, lse, dout, ctx.scale)
+            return dq, dk, dv, None, None
         seed, offset = _philox_state()
         with _sdpa_priority():
             dq, dk, dv, _ = \
                 torch.ops.aten._scaled_dot_product_efficient_attention_backward(
                     dout, q, k, v, None, out, lse, seed, offset, 0.0,
                     [True, True, True, False], True, scale=ctx.scale)
-        return dq, dk, dv, None
+        return dq, dk, dv, None, None
 
 
-def fused_causal_attention(q, k, v, scale=None):
+def fused_causal_attention(q, k, v, scale=None, fused_backward=False):
     """softmax(scale * q k^T + causal mask) v for (B, H, T, 64) bf16 views;
-    returns (B, H, T, 64) over a contiguous (B, T, H, 64) buffer."""
+    returns (B, H, T, 64) over a contiguous (B, T, H, 64) buffer.  The
+    backward is the aten efficient-attention one, or ``attn_backward`` with
+    ``fused_backward=True``."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    return _FusedCausalAttn.apply(q, k, v, float(scale))
+    return _FusedCausalAttn.apply(q, k, v, float(scale), bool(fused_backward))
