@@ -4,8 +4,9 @@ add+RMSNorm, colsum, SwiGLU, RoPE, CE) vs their torch equivalents at the
 GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
 section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
 the fused bias-gradient section, `--only-attn` the attention forward,
-`--only-attn-bwd` the attention backward, `--only-wgrad` the split-K
-weight-gradient kernel."""
+`--only-attn-bwd` the attention backward, `--only-gqa-attn` grouped-query
+attention forward and backward, `--only-wgrad` the split-K weight-gradient
+kernel."""
 import json
 import sys
 import time
@@ -297,6 +298,101 @@ def bench_attn_bwd(out, rounds=7, iters=20):
         torch.equal(a, b) for a, b in zip(first, grads))
 
 
+def bench_gqa_attn(out, rounds=7, iters=20):
+    # ---- causal grouped-query attention, forward and backward, at the
+    # profile's Llama-1B shape (B=8, T=2048) and at the shape
+    # `bench.py --model llama1b` runs by default (B=64, T=1024); Hq=32,
+    # Hkv=8, D=64, q/k/v in the model's layout.  Three arms, interleaved round
+    # by round, device-event timed, median and range over the rounds:
+    #   sdpa  the SDPA enable_gqa call the model makes (the parent); its
+    #         backward is timed as forward + backward minus forward
+    #   gqa   the new kernels (ops/fused_gqa_attn.py)
+    #   mha   the MHA kernels (ops/fused_attn.py) on repeat_interleave'd K/V;
+    #         the expansion (and, backward, the group sum of dk and dv) is
+    #         timed on its own as `expand`
+    # FLOP: the causal half of 2 (forward) or 5 (backward) B Hq T^2 D products.
+    import torch.nn.functional as F
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from sharedtensor_amd.ops import fused_attn, fused_gqa_attn
+    pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
+           SDPBackend.MATH]
+    Hq, Hkv, D = 32, 8, 64
+    G = Hq // Hkv
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for B, T in ((8, 2048), (64, 1024)):
+        mk = lambda h: torch.randn(B, T, h, D, device="cuda").to(
+            torch.bfloat16).transpose(1, 2)
+        q, k, v, dout = mk(Hq), mk(Hkv), mk(Hkv), mk(Hq)
+        assert fused_gqa_attn.can_use(q, k, v)
+        o, lse = fused_gqa_attn.gqa_forward(q, k, v)
+        ot = o.transpose(1, 2)
+        ke, ve = (x.repeat_interleave(G, dim=1) for x in (k, v))
+        gq, gke, gve = (torch.empty_like(q) for _ in range(3))
+        gk, gv = torch.empty_like(k), torch.empty_like(v)
+        delta = torch.empty(B, Hq, T, dtype=torch.float32, device="cuda")
+        qr, kr, vr = (x.detach().clone().requires_grad_() for x in (q, k, v))
+
+        def sdpa(x=q, y=k, z=v):
+            with sdpa_kernel(pri, set_priority=True):
+                return F.scaled_dot_product_attention(x, y, z, is_causal=True,
+                                                      enable_gqa=True)
+
+        def sdpa_fwd_bwd():
+            sdpa(qr, kr, vr).backward(dout)
+            qr.grad = kr.grad = vr.grad = None
+
+        def expand_bwd():
+            for x in (k, v):
+                x.repeat_interleave(G, dim=1)
+            for x in (gke, gve):
+                x.view(B, Hkv, G, T, D).sum(2)
+
+        arms = {
+            "fwd_sdpa": sdpa,
+            "fwd_gqa": lambda: fused_gqa_attn.gqa_forward(q, k, v, out=o,
+                                                          lse=lse),
+            "fwd_mha": lambda: fused_attn.attn_forward(q, ke, ve, out=o,
+                                                       lse=lse),
+            "fwd_expand": lambda: [x.repeat_interleave(G, dim=1)
+                                   for x in (k, v)],
+            "fwdbwd_sdpa": sdpa_fwd_bwd,
+            "bwd_gqa": lambda: fused_gqa_attn.gqa_backward(
+                q, k, v, ot, lse, dout, None, gq, gk, gv, delta=delta),
+            "bwd_mha": lambda: fused_attn.attn_backward(
+                q, ke, ve, ot, lse, dout, None, gq, gke, gve, delta=delta),
+            "bwd_expand": expand_bwd,
+        }
+        for fn in arms.values():
+            timed(fn)
+        ms = {n: [] for n in arms}
+        for _ in range(rounds):
+            for n, fn in arms.items():
+                ms[n].append(timed(fn))
+        ms["bwd_sdpa"] = [a - b for a, b in zip(ms["fwdbwd_sdpa"],
+                                                ms["fwd_sdpa"])]
+        flop = B * Hq * T * T * D
+        rec = dict(B=B, Hq=Hq, Hkv=Hkv, T=T, D=D, rounds=rounds, iters=iters)
+        for n, xs in ms.items():
+            xs = sorted(xs)
+            med = xs[len(xs) // 2]
+            rec[n] = dict(ms_median=round(med, 4),
+                          ms_range=[round(xs[0], 4), round(xs[-1], 4)])
+            if "expand" not in n:
+                mult = {"fwd": 2, "bwd": 5, "fwdbwd": 7}[n.split("_")[0]]
+                rec[n]["tflops"] = round(mult * flop / med / 1e9, 1)
+        out[f"gqa_attn_B{B}_T{T}"] = rec
+
+
 def load_tunableop():
     """The checked-in TunableOp GEMM table, loaded as bench.py loads it."""
     import os
@@ -382,6 +478,10 @@ def main():
         return
     if "--only-attn-bwd" in sys.argv[1:]:
         bench_attn_bwd(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-gqa-attn" in sys.argv[1:]:
+        bench_gqa_attn(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-wgrad" in sys.argv[1:]:

@@ -37,11 +37,13 @@ SOURCES = [
     "rope_kernels.hip",
     "attn_kernels.hip",
     "attn_bwd_kernels.hip",
+    "gqa_attn_kernels.hip",
+    "gqa_attn_bwd_kernels.hip",
     "wgrad_kernels.hip",
     "bindings.cpp",
 ]
 
-HEADERS = ["common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
+HEADERS = ["attn_bwd_tile.h", "common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
            "optim_step.h", "rccl_transport.h"]
 
 
@@ -54,9 +56,11 @@ HEADERS = ["common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h"
 # registers, LDS and occupancy are the same either way
 # (tests/test_attn_bwd_resource_usage.py compiles with these flags).  The
 # host pass of hipcc prints that it ignores the feature; that is expected.
+# gqa_attn_bwd_kernels.hip shares that arithmetic and gets the same entry.
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "attn_bwd_kernels.hip": ["-Xclang", "-target-feature",
-                             "-Xclang", "-packed-fp32-ops"],
+    "attn_bwd_kernels.hip": NO_PACKED_FP32,
+    "gqa_attn_bwd_kernels.hip": NO_PACKED_FP32,
 }
 
 

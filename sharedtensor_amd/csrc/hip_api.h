@@ -359,6 +359,35 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
                               const int64_t* dv_strides, int64_t lse_stride,
                               float scale, hipStream_t s);
 
+// Causal bf16 grouped-query attention forward, head dim 64
+// (gqa_attn_kernels.hip).  As hip_attn_fwd_causal_hd64, with q of Hq heads
+// and k, v of Hkv heads: Hq = G * Hkv, G in {2, 4, 8}, query head h reads kv
+// head h / G.  `out` is contiguous (B, T, Hq, 64) bf16, `lse`
+// (B, Hq, lse_stride >= T) fp32.  Throws on anything else, G = 1 included.
+void hip_gqa_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
+                                  void* out, float* lse, int64_t B, int64_t Hq,
+                                  int64_t Hkv, int64_t T,
+                                  const int64_t* q_strides,
+                                  const int64_t* k_strides,
+                                  const int64_t* v_strides, int64_t lse_stride,
+                                  float scale, hipStream_t s);
+
+// Causal bf16 grouped-query attention backward, head dim 64
+// (gqa_attn_bwd_kernels.hip).  As hip_attn_bwd_causal_hd64: q, out, dout, dq
+// have Hq heads, k, v, dk, dv have Hkv heads, `lse` is
+// (B, Hq, lse_stride >= T) and the workspace `delta` (B, Hq, T).  dk and dv
+// of a kv head are the sums over its G query heads, taken in fp32 inside one
+// workgroup and rounded once: no atomics, bit-identical across repeats.
+void hip_gqa_attn_bwd_causal_hd64(
+    const void* q, const void* k, const void* v, const void* out,
+    const void* dout, const float* lse, void* dq, void* dk, void* dv,
+    float* delta, int64_t B, int64_t Hq, int64_t Hkv, int64_t T,
+    const int64_t* q_strides, const int64_t* k_strides,
+    const int64_t* v_strides, const int64_t* out_strides,
+    const int64_t* dout_strides, const int64_t* dq_strides,
+    const int64_t* dk_strides, const int64_t* dv_strides, int64_t lse_stride,
+    float scale, hipStream_t s);
+
 // Split-K bf16 weight gradient dW[N, K] = dY[M, N]^T X[M, K]
 // (wgrad_kernels.hip), fp32 accumulation.  ldy, ldx, ldw are row strides in
 // elements (multiples of 8, pointers 16-byte aligned).  `variant` picks the

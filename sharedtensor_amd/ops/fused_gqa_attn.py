@@ -1,0 +1,167 @@
+"""Causal bf16 grouped-query attention for head dim 64 with hand-written
+forward (csrc/gqa_attn_kernels.hip) and backward
+(csrc/gqa_attn_bwd_kernels.hip) kernels: Hq = G * Hkv query heads, G in
+{2, 4, 8}, query head h reads kv head h // G (the ``enable_gqa`` /
+``repeat_interleave`` convention).
+
+``fused_causal_gqa_attention(q, k, v)`` takes q as a (B, Hq, T, 64) view and
+k, v as (B, Hkv, T, 64) views and reads them in place through their strides;
+K and V are never expanded.  The forward writes ``out`` as contiguous
+(B, T, Hq, 64), returned as its (B, Hq, T, 64) view, and ``lse`` (B, Hq, T)
+fp32.  The backward is ``gqa_backward``: two HIP kernels, dk and dv summed
+over the group in fp32 and rounded once, no atomics, bit-identical across
+repeats.
+
+``can_use`` says whether the kernels take the inputs; G = 1 is not theirs
+(ops/fused_attn.py has it).  A call outside ``can_use`` raises ``ValueError``;
+there is never a silent fall-back.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .. import _core
+from .fused_attn import HEAD_DIM, _bth, _strides_ok
+
+GROUPS = (2, 4, 8)
+
+
+def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+    """q: (B, Hq, T, 64); k, v: (B, Hkv, T, 64).  True for CUDA bf16, Hq a
+    multiple of Hkv by 2, 4 or 8, equal batch and length, a non-empty
+    problem, and the stride rules of ``fused_attn.can_use``."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda):
+        return False
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        return False
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
+        return False
+    B, Hq, T, D = q.shape
+    if D != HEAD_DIM or q.numel() == 0 or k.numel() == 0:
+        return False
+    if k.shape[0] != B or k.shape[2] != T or k.shape[3] != D:
+        return False
+    Hkv = k.shape[1]
+    if Hq % Hkv or Hq // Hkv not in GROUPS:
+        return False
+    return _strides_ok(q) and _strides_ok(k) and _strides_ok(v)
+
+
+def gqa_forward(q, k, v, scale=None, out=None, lse=None):
+    """Launch the kernel on the current stream.  Returns (out, lse): out
+    (B, T, Hq, 64) bf16 contiguous, lse (B, Hq, T) fp32.  ``out``/``lse`` may
+    be passed in (tests put guard regions around them)."""
+    if not can_use(q, k, v):
+        raise ValueError("fused_gqa_attn: inputs the kernel does not take "
+                         "(see can_use)")
+    B, Hq, T, D = q.shape
+    Hkv = k.shape[1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, Hq, T), dtype=torch.float32, device=q.device)
+    if (out.shape != (B, T, Hq, D) or not out.is_contiguous()
+            or out.dtype != torch.bfloat16 or out.device != q.device):
+        raise ValueError("fused_gqa_attn: out must be contiguous "
+                         "(B, T, Hq, 64) bf16")
+    if (lse.shape != (B, Hq, T) or not lse.is_contiguous()
+            or lse.dtype != torch.float32 or lse.device != q.device):
+        raise ValueError("fused_gqa_attn: lse must be contiguous (B, Hq, T) "
+                         "fp32")
+    s = torch.cuda.current_stream(q.device).cuda_stream
+    _core.gqa_attn_fwd_causal_hd64(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        lse.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k), _bth(v), T,
+        float(scale), s)
+    return out, lse
+
+
+def can_use_backward(q, k, v, out, lse, dout) -> bool:
+    """``can_use`` for the backward: q, k, v as there; out and dout bf16
+    (B, Hq, T, 64) views under the same stride rules; lse contiguous
+    (B, Hq, T) fp32."""
+    if not can_use(q, k, v):
+        return False
+    for t in (out, dout):
+        if not (t.is_cuda and t.dtype == torch.bfloat16
+                and t.shape == q.shape and _strides_ok(t)):
+            return False
+    return (lse.is_cuda and lse.dtype == torch.float32
+            and lse.shape == q.shape[:3] and lse.is_contiguous())
+
+
+def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
+                 dv=None, delta=None):
+    """dq (B, Hq, T, 64) and dk, dv (B, Hkv, T, 64) of ``gqa_forward`` on the
+    current stream, as views of contiguous (B, T, H, 64) bf16 buffers.  A
+    dout the kernel cannot read in place (a stride rule) is made contiguous
+    once; anything else outside ``can_use_backward`` raises.  ``dq``/``dk``/
+    ``dv`` (views to write into) and the fp32 (B, Hq, T) workspace ``delta``
+    may be passed in (tests put guard regions around them)."""
+    if (torch.is_tensor(dout) and dout.is_cuda and q.dim() == 4
+            and dout.dtype == torch.bfloat16 and dout.shape == q.shape
+            and not _strides_ok(dout)):
+        dout = dout.contiguous()
+    if not can_use_backward(q, k, v, out, lse, dout):
+        raise ValueError("fused_gqa_attn: inputs the backward kernels do not "
+                         "take (see can_use_backward)")
+    B, Hq, T, D = q.shape
+    Hkv = k.shape[1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    grads = []
+    for g, like in ((dq, q), (dk, k), (dv, v)):
+        if g is None:
+            g = torch.empty((B, T, like.shape[1], D), dtype=q.dtype,
+                            device=q.device).transpose(1, 2)
+        if (g.shape != like.shape or g.dtype != torch.bfloat16
+                or g.device != q.device or not _strides_ok(g)
+                or min(g.stride()[:3]) < D):
+            raise ValueError("fused_gqa_attn: dq, dk, dv must be bf16 "
+                             "(B, H, T, 64) views the kernel can write")
+        grads.append(g)
+    if delta is None:
+        delta = torch.empty((B, Hq, T), dtype=torch.float32, device=q.device)
+    if (delta.shape != (B, Hq, T) or not delta.is_contiguous()
+            or delta.dtype != torch.float32 or delta.device != q.device):
+        raise ValueError("fused_gqa_attn: delta must be contiguous "
+                         "(B, Hq, T) fp32")
+    dq, dk, dv = grads
+    s = torch.cuda.current_stream(q.device).cuda_stream
+    _core.gqa_attn_bwd_causal_hd64(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+        dv.data_ptr(), delta.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k),
+        _bth(v), _bth(out), _bth(dout), _bth(dq), _bth(dk), _bth(dv), T,
+        float(scale), s)
+    return dq, dk, dv
+
+
+class _FusedCausalGqaAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        out, lse = gqa_forward(q, k, v, scale)
+        out = out.transpose(1, 2)  # (B, Hq, T, D) view, as SDPA returns it
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = gqa_backward(q, k, v, out, lse, dout, ctx.scale)
+        return dq, dk, dv, None
+
+
+def fused_causal_gqa_attention(q, k, v, scale=None):
+    """softmax(scale * q k^T + causal mask) v with grouped kv heads, for bf16
+    q (B, Hq, T, 64) and k, v (B, Hkv, T, 64) views; returns (B, Hq, T, 64)
+    over a contiguous (B, T, Hq, 64) buffer.  The backward is
+    ``gqa_backward``."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    return _FusedCausalGqaAttn.apply(q, k, v, float(scale))
