@@ -5,7 +5,8 @@ GPT-2-small B=64 and llama-1B bench shapes.  `--only-rope` runs the RoPE
 section alone, `--only-add-rms` the add+RMSNorm section, `--only-bias-grad`
 the fused bias-gradient section, `--only-attn` the attention forward,
 `--only-attn-bwd` the attention backward, `--only-gqa-attn` grouped-query
-attention forward and backward, `--only-wgrad` the split-K weight-gradient
+attention forward and backward, `--only-gqa-attn-hd128` grouped-query
+attention at head dim 128, `--only-wgrad` the split-K weight-gradient
 kernel."""
 import json
 import sys
@@ -393,6 +394,81 @@ def bench_gqa_attn(out, rounds=7, iters=20):
         out[f"gqa_attn_B{B}_T{T}"] = rec
 
 
+def bench_gqa_attn_hd128(out, rounds=7, iters=20):
+    # ---- causal grouped-query attention at head dim 128 (Llama-3-8B: Hq=32,
+    # Hkv=8), q/k/v in the model's layout, at (B, T) = (8, 2048) and
+    # (2, 8192).  Arms interleaved round by round, device-event timed, median
+    # and range over the rounds:
+    #   fwd_sdpa       the SDPA enable_gqa call the model makes (the parent)
+    #   fwd_gqa128     csrc/gqa_attn_hd128_kernels.hip
+    #   fwdbwd_sdpa    forward + backward of the SDPA call through autograd
+    #   fwdbwd_gqa128  forward + backward of fused_causal_gqa_attention: our
+    #                  forward, K/V expansion, the aten backward, the group sum
+    # FLOP: the causal half of 2 (forward) or 7 (both) B Hq T^2 D products.
+    import torch.nn.functional as F
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from sharedtensor_amd.ops import fused_gqa_attn
+    pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
+           SDPBackend.MATH]
+    Hq, Hkv, D = 32, 8, 128
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for B, T in ((8, 2048), (2, 8192)):
+        mk = lambda h: torch.randn(B, T, h, D, device="cuda").to(
+            torch.bfloat16).transpose(1, 2)
+        q, k, v, dout = mk(Hq), mk(Hkv), mk(Hkv), mk(Hq)
+        assert fused_gqa_attn.can_use(q, k, v)
+        o, lse = fused_gqa_attn.gqa_forward(q, k, v)
+        qr, kr, vr = (x.detach().clone().requires_grad_() for x in (q, k, v))
+
+        def sdpa(x=q, y=k, z=v):
+            with sdpa_kernel(pri, set_priority=True):
+                return F.scaled_dot_product_attention(x, y, z, is_causal=True,
+                                                      enable_gqa=True)
+
+        def fwd_bwd(fn):
+            def run():
+                fn(qr, kr, vr).backward(dout)
+                qr.grad = kr.grad = vr.grad = None
+            return run
+
+        arms = {
+            "fwd_sdpa": sdpa,
+            "fwd_gqa128": lambda: fused_gqa_attn.gqa_forward(q, k, v, out=o,
+                                                             lse=lse),
+            "fwdbwd_sdpa": fwd_bwd(sdpa),
+            "fwdbwd_gqa128": fwd_bwd(fused_gqa_attn.fused_causal_gqa_attention),
+        }
+        for fn in arms.values():
+            timed(fn)
+        ms = {n: [] for n in arms}
+        for _ in range(rounds):
+            for n, fn in arms.items():
+                ms[n].append(timed(fn))
+        flop = B * Hq * T * T * D
+        rec = dict(B=B, Hq=Hq, Hkv=Hkv, T=T, D=D, rounds=rounds, iters=iters)
+        for n, xs in ms.items():
+            xs = sorted(xs)
+            med = xs[len(xs) // 2]
+            mult = {"fwd": 2, "fwdbwd": 7}[n.split("_")[0]]
+            rec[n] = dict(ms_median=round(med, 4),
+                          ms_range=[round(xs[0], 4), round(xs[-1], 4)],
+                          tflops=round(mult * flop / med / 1e9, 1))
+        rec["fwdbwd_gqa128_wholly_below_sdpa"] = (
+            rec["fwdbwd_gqa128"]["ms_range"][1]
+            < rec["fwdbwd_sdpa"]["ms_range"][0])
+        out[f"gqa_attn_hd128_B{B}_T{T}"] = rec
+
+
 def load_tunableop():
     """The checked-in TunableOp GEMM table, loaded as bench.py loads it."""
     import os
@@ -482,6 +558,10 @@ def main():
         return
     if "--only-gqa-attn" in sys.argv[1:]:
         bench_gqa_attn(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-gqa-attn-hd128" in sys.argv[1:]:
+        bench_gqa_attn_hd128(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-wgrad" in sys.argv[1:]:

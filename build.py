@@ -39,6 +39,7 @@ SOURCES = [
     "attn_bwd_kernels.hip",
     "gqa_attn_kernels.hip",
     "gqa_attn_bwd_kernels.hip",
+    "gqa_attn_hd128_kernels.hip",
     "wgrad_kernels.hip",
     "bindings.cpp",
 ]
@@ -57,10 +58,13 @@ HEADERS = ["attn_bwd_tile.h", "common.h", "codec_cpu.h", "device_util.h", "engin
 # (tests/test_attn_bwd_resource_usage.py compiles with these flags).  The
 # host pass of hipcc prints that it ignores the feature; that is expected.
 # gqa_attn_bwd_kernels.hip shares that arithmetic and gets the same entry.
+# gqa_attn_hd128_kernels.hip, new and never run packed either, gets it for
+# the rescale of its 64 O registers per tile.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "attn_bwd_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_bwd_kernels.hip": NO_PACKED_FP32,
+    "gqa_attn_hd128_kernels.hip": NO_PACKED_FP32,
 }
 
 

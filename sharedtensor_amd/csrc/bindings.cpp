@@ -510,6 +510,25 @@ PYBIND11_MODULE(_core, m) {
         py::arg("T"), py::arg("q_strides"), py::arg("k_strides"),
         py::arg("v_strides"), py::arg("lse_stride"), py::arg("scale"),
         py::arg("stream"));
+  m.def("gqa_attn_fwd_causal_hd128",
+        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out, uintptr_t lse,
+           int64_t B, int64_t Hq, int64_t Hkv, int64_t T, Strides3 q_strides,
+           Strides3 k_strides, Strides3 v_strides, int64_t lse_stride,
+           double scale, uintptr_t stream) {
+          hip_gqa_attn_fwd_causal_hd128(
+              reinterpret_cast<const void*>(q),
+              reinterpret_cast<const void*>(k),
+              reinterpret_cast<const void*>(v), reinterpret_cast<void*>(out),
+              reinterpret_cast<float*>(lse), B, Hq, Hkv, T, q_strides.data(),
+              k_strides.data(), v_strides.data(), lse_stride,
+              static_cast<float>(scale),
+              reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
+        py::arg("lse"), py::arg("B"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("T"), py::arg("q_strides"), py::arg("k_strides"),
+        py::arg("v_strides"), py::arg("lse_stride"), py::arg("scale"),
+        py::arg("stream"));
   m.def("gqa_attn_bwd_causal_hd64",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out,
            uintptr_t dout, uintptr_t lse, uintptr_t dq, uintptr_t dk,

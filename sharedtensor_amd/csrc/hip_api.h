@@ -372,6 +372,18 @@ void hip_gqa_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
                                   const int64_t* v_strides, int64_t lse_stride,
                                   float scale, hipStream_t s);
 
+// The same for head dim 128 (gqa_attn_hd128_kernels.hip): `out` is
+// contiguous (B, T, Hq, 128) bf16; every other rule and message is the hd64
+// launcher's.
+void hip_gqa_attn_fwd_causal_hd128(const void* q, const void* k, const void* v,
+                                   void* out, float* lse, int64_t B,
+                                   int64_t Hq, int64_t Hkv, int64_t T,
+                                   const int64_t* q_strides,
+                                   const int64_t* k_strides,
+                                   const int64_t* v_strides,
+                                   int64_t lse_stride, float scale,
+                                   hipStream_t s);
+
 // Causal bf16 grouped-query attention backward, head dim 64
 // (gqa_attn_bwd_kernels.hip).  As hip_attn_bwd_causal_hd64: q, out, dout, dq
 // have Hq heads, k, v, dk, dv have Hkv heads, `lse` is

@@ -27,6 +27,23 @@ import torch.nn.functional as F
 # kernels do not take keep the SDPA path.
 FUSE_GQA_ATTN = True
 
+# The same at head dim 128 (Llama-3-8B): our forward
+# (csrc/gqa_attn_hd128_kernels.hip), the aten efficient-attention backward on
+# K/V expanded over the group.  The flag is on only if forward + backward of
+# that path lies wholly below the SDPA enable_gqa call's range at both
+# benchmark shapes (benchmarks/bench_model_kernels.py --only-gqa-attn-hd128).
+# Measured at Hq=32, Hkv=8, range over 7 rounds: B=8, T=2048 forward +
+# backward 2.425-2.444 ms against 4.732-4.747 ms for the SDPA call (forward
+# alone 0.621 against 0.742 ms); B=2, T=8192 7.572-7.647 ms against
+# 13.188-13.229 ms (forward alone 1.999 against 2.428 ms), so it is on.  Most
+# of the gain is the backward: on expanded K/V aten picks a 1.39 ms kernel
+# where the enable_gqa call runs 4.14 ms of dk/dv and dq kernels.
+# `bench.py --model llama8b --batch 4 --seq 2048`, three steps: 402.2 ms per
+# step with the flag on against 453.5 ms off.  Numbers in profiles/r13/.
+# SHTENS_FUSED_GQA_ATTN_HD128 = 0 or 1 overrides it; it is consulted only when
+# head dim is 128.
+FUSE_GQA_ATTN_HD128 = True
+
 
 def _flag(env: str, default: bool) -> bool:
     v = os.environ.get(env)
@@ -34,7 +51,11 @@ def _flag(env: str, default: bool) -> bool:
 
 
 def _gqa_ok(q, k, v) -> bool:
-    if not (_flag("SHTENS_FUSED_GQA_ATTN", FUSE_GQA_ATTN) and q.is_cuda):
+    if q.shape[-1] == 128:
+        on = _flag("SHTENS_FUSED_GQA_ATTN_HD128", FUSE_GQA_ATTN_HD128)
+    else:
+        on = _flag("SHTENS_FUSED_GQA_ATTN", FUSE_GQA_ATTN)
+    if not (on and q.is_cuda):
         return False
     from ..ops import fused_gqa_attn
     return fused_gqa_attn.can_use(q, k, v)
@@ -160,7 +181,7 @@ class LlamaAttention(nn.Module):
             q = apply_rope(q, cos, sin)
             k = apply_rope(k, cos, sin)
         if _gqa_ok(q, k, v):
-            # q, k (rotated) and v (the (B, T, H, 64).transpose(1, 2) view)
+            # q, k (rotated) and v (the (B, T, H, D).transpose(1, 2) view)
             # are read in place through their strides; K/V are not expanded
             from ..ops import fused_gqa_attn
             y = fused_gqa_attn.fused_causal_gqa_attention(q, k, v)

@@ -1,8 +1,9 @@
 """Causal bf16 grouped-query attention for head dim 64 with hand-written
 forward (csrc/gqa_attn_kernels.hip) and backward
-(csrc/gqa_attn_bwd_kernels.hip) kernels: Hq = G * Hkv query heads, G in
-{2, 4, 8}, query head h reads kv head h // G (the ``enable_gqa`` /
-``repeat_interleave`` convention).
+(csrc/gqa_attn_bwd_kernels.hip) kernels, and for head dim 128 with a
+hand-written forward (csrc/gqa_attn_hd128_kernels.hip): Hq = G * Hkv query
+heads, G in {2, 4, 8}, query head h reads kv head h // G (the ``enable_gqa``
+/ ``repeat_interleave`` convention).
 
 ``fused_causal_gqa_attention(q, k, v)`` takes q as a (B, Hq, T, 64) view and
 k, v as (B, Hkv, T, 64) views and reads them in place through their strides;
@@ -11,6 +12,12 @@ K and V are never expanded.  The forward writes ``out`` as contiguous
 fp32.  The backward is ``gqa_backward``: two HIP kernels, dk and dv summed
 over the group in fp32 and rounded once, no atomics, bit-identical across
 repeats.
+
+At head dim 128 the same call runs our forward; its backward is the aten
+efficient-attention backward on q and on K and V expanded over the group,
+fed our ``out`` and ``lse`` (as ``fused_attn._FusedCausalAttn`` does for
+MHA), dk and dv summed over the group.  ``can_use_backward`` and
+``gqa_backward`` are head dim 64 only.
 
 ``can_use`` says whether the kernels take the inputs; G = 1 is not theirs
 (ops/fused_attn.py has it).  A call outside ``can_use`` raises ``ValueError``;
@@ -23,15 +30,17 @@ import math
 import torch
 
 from .. import _core
-from .fused_attn import HEAD_DIM, _bth, _strides_ok
+from .fused_attn import (HEAD_DIM, _bth, _philox_state, _sdpa_priority,
+                         _strides_ok)
 
 GROUPS = (2, 4, 8)
+HEAD_DIMS = (HEAD_DIM, 128)  # forward; the hand-written backward is HEAD_DIM
 
 
 def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
-    """q: (B, Hq, T, 64); k, v: (B, Hkv, T, 64).  True for CUDA bf16, Hq a
-    multiple of Hkv by 2, 4 or 8, equal batch and length, a non-empty
-    problem, and the stride rules of ``fused_attn.can_use``."""
+    """q: (B, Hq, T, D); k, v: (B, Hkv, T, D), D 64 or 128.  True for CUDA
+    bf16, Hq a multiple of Hkv by 2, 4 or 8, equal batch and length, a
+    non-empty problem, and the stride rules of ``fused_attn.can_use``."""
     if not (q.is_cuda and k.is_cuda and v.is_cuda):
         return False
     if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
@@ -39,7 +48,7 @@ def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
         return False
     B, Hq, T, D = q.shape
-    if D != HEAD_DIM or q.numel() == 0 or k.numel() == 0:
+    if D not in HEAD_DIMS or q.numel() == 0 or k.numel() == 0:
         return False
     if k.shape[0] != B or k.shape[2] != T or k.shape[3] != D:
         return False
@@ -51,8 +60,8 @@ def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
 
 def gqa_forward(q, k, v, scale=None, out=None, lse=None):
     """Launch the kernel on the current stream.  Returns (out, lse): out
-    (B, T, Hq, 64) bf16 contiguous, lse (B, Hq, T) fp32.  ``out``/``lse`` may
-    be passed in (tests put guard regions around them)."""
+    (B, T, Hq, D) bf16 contiguous, D 64 or 128, lse (B, Hq, T) fp32.
+    ``out``/``lse`` may be passed in (tests put guard regions around them)."""
     if not can_use(q, k, v):
         raise ValueError("fused_gqa_attn: inputs the kernel does not take "
                          "(see can_use)")
@@ -67,13 +76,15 @@ def gqa_forward(q, k, v, scale=None, out=None, lse=None):
     if (out.shape != (B, T, Hq, D) or not out.is_contiguous()
             or out.dtype != torch.bfloat16 or out.device != q.device):
         raise ValueError("fused_gqa_attn: out must be contiguous "
-                         "(B, T, Hq, 64) bf16")
+                         "(B, T, Hq, 64 or 128) bf16")
     if (lse.shape != (B, Hq, T) or not lse.is_contiguous()
             or lse.dtype != torch.float32 or lse.device != q.device):
         raise ValueError("fused_gqa_attn: lse must be contiguous (B, Hq, T) "
                          "fp32")
     s = torch.cuda.current_stream(q.device).cuda_stream
-    _core.gqa_attn_fwd_causal_hd64(
+    launch = (_core.gqa_attn_fwd_causal_hd64 if D == HEAD_DIM
+              else _core.gqa_attn_fwd_causal_hd128)
+    launch(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
         lse.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k), _bth(v), T,
         float(scale), s)
@@ -83,8 +94,8 @@ def gqa_forward(q, k, v, scale=None, out=None, lse=None):
 def can_use_backward(q, k, v, out, lse, dout) -> bool:
     """``can_use`` for the backward: q, k, v as there; out and dout bf16
     (B, Hq, T, 64) views under the same stride rules; lse contiguous
-    (B, Hq, T) fp32."""
-    if not can_use(q, k, v):
+    (B, Hq, T) fp32.  Head dim 64 only."""
+    if not can_use(q, k, v) or q.shape[-1] != HEAD_DIM:
         return False
     for t in (out, dout):
         if not (t.is_cuda and t.dtype == torch.bfloat16
@@ -157,11 +168,42 @@ class _FusedCausalGqaAttn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+class _FusedCausalGqaAttnHd128(torch.autograd.Function):
+    """Our forward; the aten efficient-attention backward on expanded K/V."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        out, lse = gqa_forward(q, k, v, scale)
+        out = out.transpose(1, 2)  # (B, Hq, T, D) view, as aten returns it
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        Hkv = k.shape[1]
+        G = q.shape[1] // Hkv
+        ke, ve = (t.repeat_interleave(G, dim=1) for t in (k, v))
+        seed, offset = _philox_state()
+        with _sdpa_priority():
+            dq, dk, dv, _ = \
+                torch.ops.aten._scaled_dot_product_efficient_attention_backward(
+                    dout, q, ke, ve, None, out, lse, seed, offset, 0.0,
+                    [True, True, True, False], True, scale=ctx.scale)
+        # bf16 per query head; the sum accumulates in fp32 and rounds once
+        dk, dv = (t.unflatten(1, (Hkv, G)).sum(2) for t in (dk, dv))
+        return dq, dk, dv, None
+
+
 def fused_causal_gqa_attention(q, k, v, scale=None):
     """softmax(scale * q k^T + causal mask) v with grouped kv heads, for bf16
-    q (B, Hq, T, 64) and k, v (B, Hkv, T, 64) views; returns (B, Hq, T, 64)
-    over a contiguous (B, T, Hq, 64) buffer.  The backward is
-    ``gqa_backward``."""
+    q (B, Hq, T, D) and k, v (B, Hkv, T, D) views, D 64 or 128; returns
+    (B, Hq, T, D) over a contiguous (B, T, Hq, D) buffer.  The backward is
+    ``gqa_backward`` at D = 64 and the aten efficient-attention backward on
+    expanded K/V at D = 128.  Inputs outside ``can_use`` raise."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if torch.is_tensor(q) and q.dim() == 4 and q.shape[-1] == 128:
+        return _FusedCausalGqaAttnHd128.apply(q, k, v, float(scale))
     return _FusedCausalGqaAttn.apply(q, k, v, float(scale))

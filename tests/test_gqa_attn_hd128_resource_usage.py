@@ -1,0 +1,34 @@
+"""Compiler resource report of csrc/gqa_attn_hd128_kernels.hip (no GPU
+needed), both instantiations held to the plan in its header comment: no
+scratch, no spills, 64 KB of LDS, 2 waves/SIMD, VGPRs plus AGPRs within that
+step's 256 registers."""
+import pytest
+
+import build
+from resource_report import kernel_resources
+
+VGPR_FILE = 512  # unified VGPR + AGPR budget of one SIMD lane
+SRC = "gqa_attn_hd128_kernels.hip"
+PLAN = {"k_gqa_fwd_hd128ILi2E": dict(waves=2, lds=64 * 1024),
+        "k_gqa_fwd_hd128ILi4E": dict(waves=2, lds=64 * 1024)}
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    with pytest.MonkeyPatch.context() as mp:  # hipcc appends these itself
+        mp.setenv("HIPCC_COMPILE_FLAGS_APPEND", " ".join(build.EXTRA_FLAGS[SRC]))
+        found = kernel_resources(SRC, tmp_path_factory.mktemp("gqa_hd128"))
+    assert len(found) == len(PLAN), sorted(found)  # every instantiation
+    return found
+
+
+@pytest.mark.parametrize("name", sorted(PLAN))
+def test_gqa_hd128_kernel_follows_plan(kernels, name):
+    plan = PLAN[name]
+    (res,) = [v for k, v in kernels.items() if name in k]
+    assert res["ScratchSize"] == 0, res
+    assert res["VGPRs Spill"] == 0 and res["SGPRs Spill"] == 0, res
+    regs = -(-res["VGPRs"] // 8) * 8 + -(-res["AGPRs"] // 8) * 8
+    assert regs <= VGPR_FILE // plan["waves"], res
+    assert res["LDS"] == plan["lds"], res
+    assert res["Occupancy"] == plan["waves"], res
