@@ -7,7 +7,8 @@ the fused bias-gradient section, `--only-attn` the attention forward,
 `--only-attn-bwd` the attention backward, `--only-gqa-attn` grouped-query
 attention forward and backward, `--only-gqa-attn-hd128` grouped-query
 attention at head dim 128, `--only-wgrad` the split-K weight-gradient
-kernel."""
+kernel, `--only-qkv-attn-bwd` the attention backward into the packed dqkv
+with the bias-gradient epilogue, and the second-stage column reduce."""
 import json
 import sys
 import time
@@ -469,6 +470,122 @@ def bench_gqa_attn_hd128(out, rounds=7, iters=20):
         out[f"gqa_attn_hd128_B{B}_T{T}"] = rec
 
 
+def _interleaved(arms, rounds, iters):
+    """Device-event time per call of each arm: one warm pass, then `rounds`
+    rounds of `iters` calls, arms interleaved.  {arm: sorted ms}."""
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for fn in arms.values():
+        timed(fn)
+    ms = {n: [] for n in arms}
+    for _ in range(rounds):
+        for n, fn in arms.items():
+            ms[n].append(timed(fn))
+    return {n: sorted(xs) for n, xs in ms.items()}
+
+
+def bench_qkv_attn_bwd(out, rounds=7, iters=20):
+    # ---- attention backward up to the packed dqkv and qkv.bias.grad at
+    # B=64 H=12 T=1024.  Parent arm: attn_backward into three separate
+    # (B, T, H, 64) buffers, then pack3_colsum.  Branch arm: attn_backward
+    # into the three views of dqkv with the column-sum epilogue, then
+    # k_colsum_reduce (inside the same call).  "plain" is attn_backward alone
+    # into separate buffers: branch minus plain is what the epilogue, the
+    # packed stores and the reduce cost together.
+    from sharedtensor_amd.ops import fused_attn
+    B, H, T, D = 64, 12, 1024, 64
+    C = H * D
+    s = torch.cuda.current_stream().cuda_stream
+    qkv = torch.randn(B, T, 3 * C, device="cuda").to(torch.bfloat16)
+    q, k, v = fused_attn._heads(qkv, H)
+    dout = torch.randn(B, T, H, D, device="cuda").to(
+        torch.bfloat16).transpose(1, 2)
+    o, lse = fused_attn.attn_forward(q, k, v)
+    o = o.transpose(1, 2)
+    sep = [torch.empty(B, T, H, D, dtype=torch.bfloat16, device="cuda")
+           for _ in range(3)]
+    sep_v = [g.transpose(1, 2) for g in sep]
+    delta = torch.empty(B, H, T, dtype=torch.float32, device="cuda")
+    dqkv_p = torch.empty(B, T, 3 * C, dtype=torch.bfloat16, device="cuda")
+    dqkv_b = torch.empty_like(dqkv_p)
+    db_p = torch.empty(3 * C, dtype=torch.bfloat16, device="cuda")
+    db_b = torch.empty_like(db_p)
+    part_p = torch.empty(_core.bias_grad_partial_floats(3 * C),
+                         dtype=torch.float32, device="cuda")
+    part_b = torch.empty(_core.attn_bwd_colsum_floats(B, H, T),
+                         dtype=torch.float32, device="cuda")
+    views = fused_attn._heads(dqkv_b, H)
+
+    def plain():
+        fused_attn.attn_backward(q, k, v, o, lse, dout, None, *sep_v,
+                                 delta=delta)
+
+    def parent():
+        plain()
+        _core.pack3_colsum(sep[0].data_ptr(), sep[1].data_ptr(),
+                           sep[2].data_ptr(), dqkv_p.data_ptr(),
+                           db_p.data_ptr(), part_p.data_ptr(), B * T, C, s)
+
+    def branch():
+        fused_attn.attn_backward(q, k, v, o, lse, dout, None, *views,
+                                 delta=delta, partial=part_b, db=db_b)
+
+    ms = _interleaved({"parent_attn_bwd_pack3": parent,
+                       "branch_attn_bwd_packed": branch,
+                       "plain_attn_bwd": plain}, rounds, iters)
+    out["qkv_attn_bwd_shape"] = dict(B=B, H=H, T=T, D=D, rounds=rounds,
+                                     iters=iters)
+    for n, xs in ms.items():
+        out[n + "_ms_median"] = round(xs[len(xs) // 2], 4)
+        out[n + "_ms_range"] = [round(xs[0], 4), round(xs[-1], 4)]
+    out["branch_max_below_parent_min"] = bool(
+        ms["branch_attn_bwd_packed"][-1] < ms["parent_attn_bwd_pack3"][0])
+    torch.cuda.synchronize()
+    out["dqkv_bit_equal"] = bool(torch.equal(dqkv_p, dqkv_b))
+    out["db_max_abs_diff"] = float((db_p.float() - db_b.float()).abs().max())
+
+    # ---- the second-stage column reduce against k_add_ln_reduce on the
+    # add+LayerNorm partials: G = 1024 rows of 3 C (with proj-bias grad) and
+    # 2 C (without) floats, C = 768
+    G = 1024
+    for nsc in (2304, 1536):
+        part = torch.randn(G * nsc, device="cuda")
+        o_old = torch.empty(3, C, dtype=torch.bfloat16, device="cuda")
+        o_new = torch.empty_like(o_old)
+        third = nsc == 3 * C
+
+        def old():
+            _core.add_ln_reduce(part.data_ptr(), G, nsc, C,
+                                o_old[0].data_ptr(), o_old[1].data_ptr(),
+                                o_old[2].data_ptr() if third else 0, s)
+
+        def new():
+            _core.colsum_reduce(part.data_ptr(), G, nsc, C,
+                                o_new[0].data_ptr(), o_new[1].data_ptr(),
+                                o_new[2].data_ptr() if third else 0, s)
+
+        ms = _interleaved({"k_add_ln_reduce": old, "k_colsum_reduce": new},
+                          rounds, 10 * iters)
+        for n, xs in ms.items():
+            key = f"{n}_G{G}_N{nsc}"
+            out[key + "_us_median"] = round(1e3 * xs[len(xs) // 2], 2)
+            out[key + "_us_range"] = [round(1e3 * xs[0], 2),
+                                      round(1e3 * xs[-1], 2)]
+        out[f"colsum_reduce_max_below_add_ln_min_N{nsc}"] = bool(
+            ms["k_colsum_reduce"][-1] < ms["k_add_ln_reduce"][0])
+        rows = 3 if third else 2
+        out[f"reduce_max_abs_diff_N{nsc}"] = float(
+            (o_old[:rows].float() - o_new[:rows].float()).abs().max())
+
+
 def load_tunableop():
     """The checked-in TunableOp GEMM table, loaded as bench.py loads it."""
     import os
@@ -566,6 +683,10 @@ def main():
         return
     if "--only-wgrad" in sys.argv[1:]:
         bench_wgrad(out, sweep="--sweep" in sys.argv[1:])
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-qkv-attn-bwd" in sys.argv[1:]:
+        bench_qkv_attn_bwd(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-add-rms" in sys.argv[1:]:

@@ -14,9 +14,9 @@
 // In backward a lane owns the same 4*NV columns for every row of its
 // grid-stride loop, so the column sums live in registers (NV is a template
 // parameter for that reason, see LN_MAXC in ln_kernels.hip).  They leave the
-// kernel as one fp32 partial row per block; k_add_ln_reduce sums the
-// partials in a fixed order and writes bf16 — no float atomics, so backward
-// repeats bit for bit.
+// kernel as one fp32 partial row per block; k_colsum_reduce
+// (bias_grad_kernels.hip) sums the partials in a fixed order and writes
+// bf16 — no float atomics, so backward repeats bit for bit.
 //
 // Other widths keep using the block-per-row kernels in ln_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -245,6 +245,9 @@ __global__ __launch_bounds__(ALN_BWD_THREADS) void k_add_ln_bwd(
     pout[i] = red[i];
 }
 
+// The second stage hip_add_ln_bwd used before k_colsum_reduce replaced it;
+// kept, behind hip_add_ln_reduce, as the other arm of that measurement
+// (benchmarks/bench_model_kernels.py --only-qkv-attn-bwd).
 // Sums the G partial rows column by column and writes bf16.  A block owns 16
 // columns; its 16 row-groups each sum every 16th partial row, then thread
 // row-group 0 adds the 16 group sums in order.  nsc = NS * C.
@@ -370,9 +373,20 @@ void hip_add_ln_bwd(const void* dy, const void* x_new, const void* w,
       launch(k_add_ln_bwd<NV(), false>, cache[NV() - 1][0]);
     });
   HIP_CHECK(hipGetLastError());
-  const int nsc = (ddbias ? 3 : 2) * C;
+  // the shared second stage (bias_grad_kernels.hip): 5.6 us against 8.3 us
+  // for k_add_ln_reduce on 1024 x 2304 partials, 4.7 against 8.3 on
+  // 1024 x 1536 (profiles/r14/)
+  hip_colsum_reduce(partial, grid, (ddbias ? 3 : 2) * C, C, dgamma, dbeta,
+                    ddbias, s);
+}
+
+void hip_add_ln_reduce(const float* partial, int G, int nsc, int C,
+                       void* dgamma, void* dbeta, void* ddbias,
+                       hipStream_t s) {
+  if (G <= 0 || C <= 0 || nsc % 16 || (nsc != 2 * C && nsc != 3 * C))
+    throw std::runtime_error("add_ln: bad reduce shape");
   hipLaunchKernelGGL(k_add_ln_reduce, dim3(nsc / 16), dim3(256), 0, s, partial,
-                     grid, nsc, C, static_cast<uint16_t*>(dgamma),
+                     G, nsc, C, static_cast<uint16_t*>(dgamma),
                      static_cast<uint16_t*>(dbeta),
                      static_cast<uint16_t*>(ddbias));
   HIP_CHECK(hipGetLastError());

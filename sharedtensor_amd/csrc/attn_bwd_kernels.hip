@@ -49,7 +49,7 @@
 //     that every global store is a whole 128-byte row.
 //   * Grid: the forward's (query blocks of one (b, h) consecutive on one
 //     XCD, heaviest (last) block first).
-//   * Resources: amdgpu_waves_per_eu(3, 3): at most 160 VGPRs (154 as
+//   * Resources: amdgpu_waves_per_eu(3, 3): at most 160 VGPRs (156 as
 //     built; 168 is the limit of the occupancy step), no AGPRs, no scratch,
 //     no spills, 32 KB of LDS -> 3 waves/SIMD, 3 workgroups per CU.
 //     Q, dO, dQ^T, S^T, dP^T, dS^T and the 16 staging registers are 136
@@ -78,6 +78,20 @@
 //     scratch, no spills -> 2 waves/SIMD, 2 workgroups per CU (LDS would
 //     allow 4).
 //
+// Column sums (qkv.bias.grad).  With the partials pointers set (csq; csk and
+// csv), the store epilogue also sums, per column, the bf16 values it stores
+// (store_rows_colsum, colsum_partial_rows in attn_bwd_tile.h): 4 rows per
+// lane, the 8 lanes of a chunk, then the 4 waves through the staging LDS the
+// wave has just read, so LDS stays at 32 KB and 33 KB.  The workgroup writes
+// 64 fp32 sums per output to row b * nblocks + block, columns 64 h.. of its
+// output's third of the 3C-wide partial row; k_colsum_reduce
+// (bias_grad_kernels.hip) sums the rows.  Fixed order, no atomics.  The
+// pointers are kernel arguments checked at run time, not a second
+// instantiation: the null path costs one scalar branch, the epilogue's eight
+// sums live in registers the accumulators have left (156 and 198 VGPRs as
+// built, the occupancy steps are unchanged), and one code object keeps the
+// plain path of the A/B arm identical to the kernel that is shipped.
+//
 // Every T is bounds-checked: rows at or past T are read as zeros (never from
 // memory) and never stored.
 #include <hip/hip_runtime.h>
@@ -101,7 +115,8 @@ __global__ __launch_bounds__(256)
     const uint16_t* __restrict__ dout, const float* __restrict__ lse,
     uint16_t* __restrict__ dq, float* __restrict__ delta, int nbh, int H,
     int T, int nqb, BwdStrides sq, BwdStrides sk, BwdStrides sv, BwdStrides so,
-    BwdStrides sdo, BwdStrides sdq, int64_t lse_stride, float scale) {
+    BwdStrides sdo, BwdStrides sdq, int64_t lse_stride, float scale,
+    float* __restrict__ csq, int64_t cs_ld) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * kTileBytes];
   // K buffers at 0 and kTileBytes, V buffers behind them
   unsigned char* const ldsK = lds;
@@ -238,7 +253,15 @@ __global__ __launch_bounds__(256)
   unsigned char* const Ow = lds + wave * (kRW * 128);
   stage_rows(Ow, acc, scale, r, hi);
   __syncthreads();
-  store_rows(Ow, dq + b * sdq.b + h * sdq.h, sdq.t, qw0, T, lane);
+  uint16_t* const dqp = dq + b * sdq.b + h * sdq.h;
+  if (!csq) {  // kernel argument: the whole workgroup takes one side
+    store_rows(Ow, dqp, sdq.t, qw0, T, lane);
+    return;
+  }
+  float cs[1][8];
+  store_rows_colsum(Ow, dqp, sdq.t, qw0, T, lane, cs[0]);
+  float* const part[1] = {csq + ((int64_t)b * nqb + qb) * cs_ld + h * kD};
+  colsum_partial_rows<1>(lds, kRW * 128, wave, tid, cs, part);
 }
 
 // ------------------------------------------------------------- dK, dV
@@ -251,7 +274,8 @@ __global__ __launch_bounds__(256)
     uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int nbh, int H,
     int T, int nkb, BwdStrides sq, BwdStrides sk, BwdStrides sv,
     BwdStrides sdo, BwdStrides sdk, BwdStrides sdv, int64_t lse_stride,
-    float scale) {
+    float scale, float* __restrict__ csk, float* __restrict__ csv,
+    int64_t cs_ld) {
   __shared__ __attribute__((aligned(16))) unsigned char
       lds[4 * kTileBytes + 2 * 2 * kTile * 4];
   // Q buffers at 0 and kTileBytes, dO buffers behind them, then per buffer
@@ -405,8 +429,19 @@ __global__ __launch_bounds__(256)
   stage_rows(Ow, dka, scale, r, hi);
   stage_rows(Ow + kRW * 128, dva, 1.f, r, hi);
   __syncthreads();
-  store_rows(Ow, dk + b * sdk.b + h * sdk.h, sdk.t, kw0, T, lane);
-  store_rows(Ow + kRW * 128, dv + b * sdv.b + h * sdv.h, sdv.t, kw0, T, lane);
+  uint16_t* const dkp = dk + b * sdk.b + h * sdk.h;
+  uint16_t* const dvp = dv + b * sdv.b + h * sdv.h;
+  if (!csk) {  // kernel argument: the whole workgroup takes one side
+    store_rows(Ow, dkp, sdk.t, kw0, T, lane);
+    store_rows(Ow + kRW * 128, dvp, sdv.t, kw0, T, lane);
+    return;
+  }
+  float cs[2][8];
+  store_rows_colsum(Ow, dkp, sdk.t, kw0, T, lane, cs[0]);
+  store_rows_colsum(Ow + kRW * 128, dvp, sdv.t, kw0, T, lane, cs[1]);
+  const int64_t poff = ((int64_t)b * nkb + kblk) * cs_ld + h * kD;
+  float* const part[2] = {csk + poff, csv + poff};
+  colsum_partial_rows<2>(lds, 2 * kRW * 128, wave, tid, cs, part);
 }
 
 }  // namespace
@@ -419,8 +454,13 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
                               const int64_t* vs, const int64_t* os,
                               const int64_t* dos, const int64_t* dqs,
                               const int64_t* dks, const int64_t* dvs,
-                              int64_t lse_stride, float scale, hipStream_t s) {
+                              int64_t lse_stride, float scale,
+                              float* colsum_partial, void* db, hipStream_t s) {
   const char* op = "attn_bwd_causal_hd64";
+  if ((colsum_partial == nullptr) != (db == nullptr))
+    throw std::runtime_error(std::string(op) +
+                             ": colsum_partial and db go together");
+  check_align(colsum_partial, 16, op, "colsum_partial");
   if (B <= 0 || H <= 0 || T <= 0)
     throw std::runtime_error(std::string(op) + ": empty problem");
   if (!(scale > 0.f) || scale > 3.0e38f)
@@ -470,6 +510,7 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
   }
   const int64_t nblk = (T + kRB - 1) / kRB;
   const int64_t nbh = B * H;
+  const int64_t C = H * kD;  // a partial row is [dq | dk | dv], C columns each
   const int64_t grid = (nbh + kXcd - 1) / kXcd * kXcd * nblk;
   if (grid > 0x7fffffff || T > (1 << 30) || nbh > 0x7fffffff)
     throw std::runtime_error(std::string(op) + ": problem too large");
@@ -479,14 +520,24 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
       u16(q), u16(k), u16(v), u16(out), u16(dout), lse,
       static_cast<uint16_t*>(dq), delta, (int)nbh, (int)H, (int)T, (int)nblk,
       st3(qs), st3(ks), st3(vs), st3(os), st3(dos), st3(dqs), lse_stride,
-      scale);
+      scale, colsum_partial, 3 * C);
   HIP_CHECK(hipGetLastError());
   k_attn_bwd_dkdv<<<dim3((unsigned)grid), dim3(256), 0, s>>>(
       u16(q), u16(k), u16(v), u16(dout), lse, delta,
       static_cast<uint16_t*>(dk), static_cast<uint16_t*>(dv), (int)nbh, (int)H,
       (int)T, (int)nblk, st3(qs), st3(ks), st3(vs), st3(dos), st3(dks),
-      st3(dvs), lse_stride, scale);
+      st3(dvs), lse_stride, scale, colsum_partial ? colsum_partial + C : nullptr,
+      colsum_partial ? colsum_partial + 2 * C : nullptr, 3 * C);
   HIP_CHECK(hipGetLastError());
+  if (colsum_partial)
+    hip_colsum_reduce(colsum_partial, B * nblk, 3 * C, 3 * C, db, nullptr,
+                      nullptr, s);
+}
+
+int64_t hip_attn_bwd_colsum_floats(int64_t B, int64_t H, int64_t T) {
+  if (B <= 0 || H <= 0 || T <= 0)
+    throw std::runtime_error("attn_bwd_causal_hd64: empty problem");
+  return B * ((T + kRB - 1) / kRB) * 3 * H * kD;
 }
 
 }  // namespace shamd

@@ -1,7 +1,8 @@
 // Tile helpers of the attention backward kernels for head dim 64, shared by
 // attn_bwd_kernels.hip (MHA) and gqa_attn_bwd_kernels.hip (GQA): the LDS tile
 // swizzle, the two LDS read patterns that feed mfma_f32_32x32x16_bf16, the
-// workgroup-to-XCD grid map and the staged whole-row epilogue.  The header
+// workgroup-to-XCD grid map and the staged whole-row epilogue, with and
+// without the column sums of what it stores (MHA only).  The header
 // comment of attn_bwd_kernels.hip derives the swizzle and the lane layouts.
 // Everything sits in an anonymous namespace: each kernel file gets its own
 // copy, inlined.
@@ -152,6 +153,83 @@ __device__ __forceinline__ void store_rows(const unsigned char* Ow,
     int gr = row0 + row;
     if (gr < T)
       *reinterpret_cast<u32x4*>(dst + (int64_t)gr * row_stride + 8 * ch) = val;
+  }
+}
+
+// store_rows that also sums, per column, the bf16 values it stores.  A lane
+// meets the same 16-byte chunk (8 columns) in all four passes, so the sums of
+// its rows pass, pass + 8, ... live in cs[0..7], added in pass order.  Rows at
+// or past T are neither stored nor summed.
+__device__ __forceinline__ void store_rows_colsum(const unsigned char* Ow,
+                                                  uint16_t* dst,
+                                                  int64_t row_stride, int row0,
+                                                  int T, int lane,
+                                                  float (&cs)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) cs[e] = 0.f;
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    int row = pass * 8 + (lane >> 3), ch = lane & 7;
+    u32x4 val = *reinterpret_cast<const u32x4*>(Ow + t_off(row, ch));
+    int gr = row0 + row;
+    if (gr < T) {
+      *reinterpret_cast<u32x4*>(dst + (int64_t)gr * row_stride + 8 * ch) = val;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        cs[2 * i] += __builtin_bit_cast(float, val[i] << 16);
+        cs[2 * i + 1] += __builtin_bit_cast(float, val[i] & 0xffff0000u);
+      }
+    }
+  }
+}
+
+// Column sums of a workgroup's NOUT staged outputs -> one fp32 partial row of
+// 64 columns per output.  cs[o]: the lane's sums from store_rows_colsum.
+// The 8 lanes of a wave that share a chunk (lane, lane ^ 8, ^ 16, ^ 32) are
+// added as a butterfly: both sides of an exchange add the same two numbers,
+// so every lane ends with the same bits.  Then each wave puts its NOUT x 64
+// sums at the start of its own staging area (`wave_bytes` apart, its rows
+// are read by then) and thread 64 o + c adds the four waves of column c of
+// output o in wave order.  Every thread of the workgroup calls it.
+template <int NOUT>
+__device__ __forceinline__ void colsum_partial_rows(unsigned char* lds,
+                                                    int wave_bytes, int wave,
+                                                    int tid,
+                                                    float (&cs)[NOUT][8],
+                                                    float* const (&dst)[NOUT]) {
+  const int lane = tid & 63;
+#pragma unroll
+  for (int m = 8; m < 64; m <<= 1)
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        cs[o][e] += __builtin_bit_cast(
+            float, __builtin_amdgcn_ds_bpermute(
+                       (lane ^ m) << 2, __builtin_bit_cast(int, cs[o][e])));
+  // orders the reads of the staged rows before the overwrite
+  __syncthreads();
+  if (lane < 8) {
+    float* mine = reinterpret_cast<float*>(lds + wave * wave_bytes) + 8 * lane;
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+      f32x4 a = {cs[o][0], cs[o][1], cs[o][2], cs[o][3]};
+      f32x4 b = {cs[o][4], cs[o][5], cs[o][6], cs[o][7]};
+      *reinterpret_cast<f32x4*>(mine + kD * o) = a;
+      *reinterpret_cast<f32x4*>(mine + kD * o + 4) = b;
+    }
+  }
+  __syncthreads();
+  if (tid < NOUT * kD) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+      t += reinterpret_cast<const float*>(lds + w * wave_bytes)[tid];
+    float* d = dst[0];
+#pragma unroll
+    for (int o = 1; o < NOUT; ++o)
+      if (tid >= o * kD) d = dst[o];
+    d[tid % kD] = t;
   }
 }
 

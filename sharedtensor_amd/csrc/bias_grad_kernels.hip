@@ -6,6 +6,9 @@
 //                      and the 3C column sums of what was copied
 //                      (the backward of qkv.split plus qkv.bias.grad)
 //   k_bg_reduce        per-block partial rows -> bf16 column sums
+//   k_colsum_reduce    the same for up to 1024 partial rows: the attention
+//                      backward's column-sum partials (attn_bwd_kernels.hip)
+//                      and the add+LayerNorm partials (add_ln_kernels.hip)
 //
 // Layout.  The N columns are N/8 column groups of 8 bf16 (one 16-byte
 // access).  A 1024-thread block is CT column threads x RT = 1024/CT row
@@ -199,6 +202,76 @@ __global__ __launch_bounds__(256) void k_bg_reduce(
     for (int i = 0; i < 8; ++i) t += red[i][cg];
     out[j] = f32_to_bf16(t);
   }
+}
+
+// The second stage for many partial rows (G up to 1024 rows of N = 2304
+// columns: the attention backward's and the add+LayerNorm's partials).  A
+// 1024-thread block owns CR_COLS = 64 columns, 16 column threads of one
+// float4 each, so every row segment it reads is 256 contiguous bytes, and 64
+// row groups: row group y sums the rows y, y + 64, ... in row order, the
+// loads of four rows in flight.  Then thread (q, c) adds the row groups 4 q
+// .. 4 q + 3 of column c in order, and thread (0, c) the 16 results in order:
+// one fixed tree, ceil(G / 64) + 4 + 16 adds deep.  A column tile cannot be
+// narrower than the 256-byte segment, so the grid is N / 64 blocks (36 at
+// N = 2304); no partial row is shared between blocks and nothing is combined
+// across blocks.  Resources: at most 64 VGPRs, 20 KB of LDS, no scratch ->
+// 8 waves/SIMD (tests/test_qkv_attn_bwd_resource_usage.py).
+constexpr int CR_THREADS = 1024;
+constexpr int CR_COLS = 64;
+constexpr int CR_RG = CR_THREADS / (CR_COLS / 4);  // 64 row groups
+
+__global__ __launch_bounds__(CR_THREADS) void k_colsum_reduce(
+    const float* __restrict__ partial, int G, int64_t N, int64_t seg,
+    uint16_t* __restrict__ o0, uint16_t* __restrict__ o1,
+    uint16_t* __restrict__ o2) {
+  __shared__ __attribute__((aligned(16))) float red[CR_RG][CR_COLS];
+  __shared__ float red2[CR_RG / 4][CR_COLS];
+  const int ct = threadIdx.x & 15, rg = threadIdx.x >> 4;
+  const int64_t c0 = static_cast<int64_t>(blockIdx.x) * CR_COLS + 4 * ct;
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c0 < N) {  // N is a multiple of 4: the whole float4 is inside
+#pragma unroll 4
+    for (int g = rg; g < G; g += CR_RG) {
+      const float4 p = *reinterpret_cast<const float4*>(
+          partial + static_cast<int64_t>(g) * N + c0);
+      a.x += p.x;
+      a.y += p.y;
+      a.z += p.z;
+      a.w += p.w;
+    }
+  }
+  *reinterpret_cast<float4*>(&red[rg][4 * ct]) = a;
+  __syncthreads();
+  const int c = threadIdx.x & (CR_COLS - 1), q = threadIdx.x / CR_COLS;
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t += red[4 * q + i][c];
+  red2[q][c] = t;
+  __syncthreads();
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * CR_COLS + c;
+  if (q == 0 && j < N) {
+    float u = 0.f;
+#pragma unroll
+    for (int i = 0; i < CR_RG / 4; ++i) u += red2[i][c];
+    const int64_t si = j / seg;
+    uint16_t* out = si == 0 ? o0 : (si == 1 ? o1 : o2);
+    if (out) out[j - si * seg] = f32_to_bf16(u);
+  }
+}
+
+void hip_colsum_reduce(const float* partial, int64_t G, int64_t N, int64_t seg,
+                       void* o0, void* o1, void* o2, hipStream_t s) {
+  if (G <= 0 || G > 0x7fffffff || N <= 0 || N % 4 || seg <= 0 || N > 3 * seg)
+    throw std::runtime_error("colsum_reduce: bad shape");
+  if (!partial) throw std::runtime_error("colsum_reduce: null partial");
+  check_align(partial, 16, "colsum_reduce", "partial");
+  const int64_t gx = (N + CR_COLS - 1) / CR_COLS;
+  if (gx > 0x7fffffff) throw std::runtime_error("colsum_reduce: too wide");
+  hipLaunchKernelGGL(k_colsum_reduce, dim3(static_cast<uint32_t>(gx)),
+                     dim3(CR_THREADS), 0, s, partial, static_cast<int>(G), N,
+                     seg, static_cast<uint16_t*>(o0),
+                     static_cast<uint16_t*>(o1), static_cast<uint16_t*>(o2));
+  HIP_CHECK(hipGetLastError());
 }
 
 static void bg_check_shape(int64_t R, int64_t N) {

@@ -426,6 +426,14 @@ PYBIND11_MODULE(_core, m) {
                         reinterpret_cast<float*>(partial), R, C,
                         reinterpret_cast<hipStream_t>(stream));
   });
+  m.def("colsum_reduce", [](uintptr_t partial, int64_t G, int64_t N,
+                            int64_t seg, uintptr_t o0, uintptr_t o1,
+                            uintptr_t o2, uintptr_t stream) {
+    hip_colsum_reduce(reinterpret_cast<const float*>(partial), G, N, seg,
+                      reinterpret_cast<void*>(o0), reinterpret_cast<void*>(o1),
+                      reinterpret_cast<void*>(o2),
+                      reinterpret_cast<hipStream_t>(stream));
+  });
   m.def("pack3_colsum", [](uintptr_t s0, uintptr_t s1, uintptr_t s2,
                            uintptr_t dst, uintptr_t db, uintptr_t partial,
                            int64_t R, int64_t C, uintptr_t stream) {
@@ -467,7 +475,8 @@ PYBIND11_MODULE(_core, m) {
            Strides3 q_strides, Strides3 k_strides, Strides3 v_strides,
            Strides3 out_strides, Strides3 dout_strides, Strides3 dq_strides,
            Strides3 dk_strides, Strides3 dv_strides, int64_t lse_stride,
-           double scale, uintptr_t stream) {
+           double scale, uintptr_t stream, uintptr_t colsum_partial,
+           uintptr_t db) {
           hip_attn_bwd_causal_hd64(
               reinterpret_cast<const void*>(q),
               reinterpret_cast<const void*>(k),
@@ -480,6 +489,8 @@ PYBIND11_MODULE(_core, m) {
               k_strides.data(), v_strides.data(), out_strides.data(),
               dout_strides.data(), dq_strides.data(), dk_strides.data(),
               dv_strides.data(), lse_stride, static_cast<float>(scale),
+              reinterpret_cast<float*>(colsum_partial),
+              reinterpret_cast<void*>(db),
               reinterpret_cast<hipStream_t>(stream));
         },
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
@@ -488,7 +499,9 @@ PYBIND11_MODULE(_core, m) {
         py::arg("T"), py::arg("q_strides"), py::arg("k_strides"),
         py::arg("v_strides"), py::arg("out_strides"), py::arg("dout_strides"),
         py::arg("dq_strides"), py::arg("dk_strides"), py::arg("dv_strides"),
-        py::arg("lse_stride"), py::arg("scale"), py::arg("stream"));
+        py::arg("lse_stride"), py::arg("scale"), py::arg("stream"),
+        py::arg("colsum_partial") = 0, py::arg("db") = 0);
+  m.def("attn_bwd_colsum_floats", &hip_attn_bwd_colsum_floats);
 
   // causal bf16 grouped-query attention, head dim 64, forward and backward
   m.def("gqa_attn_fwd_causal_hd64",
@@ -803,6 +816,15 @@ PYBIND11_MODULE(_core, m) {
                    reinterpret_cast<float*>(rstd), R, C,
                    static_cast<float>(eps),
                    reinterpret_cast<hipStream_t>(stream));
+  });
+  m.def("add_ln_reduce", [](uintptr_t partial, int G, int nsc, int C,
+                            uintptr_t dgamma, uintptr_t dbeta,
+                            uintptr_t ddbias, uintptr_t stream) {
+    hip_add_ln_reduce(reinterpret_cast<const float*>(partial), G, nsc, C,
+                      reinterpret_cast<void*>(dgamma),
+                      reinterpret_cast<void*>(dbeta),
+                      reinterpret_cast<void*>(ddbias),
+                      reinterpret_cast<hipStream_t>(stream));
   });
   m.def("add_ln_bwd", [](uintptr_t dy, uintptr_t x_new, uintptr_t w,
                          uintptr_t mean, uintptr_t rstd, uintptr_t d_x_new,

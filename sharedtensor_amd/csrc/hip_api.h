@@ -173,6 +173,10 @@ void hip_add_ln_bwd(const void* dy, const void* x_new, const void* w,
                     const float* mean, const float* rstd, const void* d_x_new,
                     void* dx_total, void* dgamma, void* dbeta, void* ddbias,
                     float* partial, int64_t R, int C, hipStream_t s);
+// The second kernel of bwd on its own (benchmarks time it against
+// hip_colsum_reduce): G partial rows of nsc = 2 C or 3 C floats.
+void hip_add_ln_reduce(const float* partial, int G, int nsc, int C,
+                       void* dgamma, void* dbeta, void* ddbias, hipStream_t s);
 
 // Column sum of (R, C) bf16 into fp32 out[C] (Linear backward bias grad);
 // caller zeroes `out` first.
@@ -314,7 +318,14 @@ void hip_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n,
 // hip_bias_grad_sweep_rows: rows one iteration of the grid's row loop covers
 // for an (R, N) output of the GELU kernel or, with `pack`, of the pack kernel
 // (tests size their grid-stride cases with it).
+//   colsum_reduce:   the second stage on its own: G fp32 partial rows of N
+//                    columns (N a multiple of 4, rows N floats apart, 16-byte
+//                    aligned) -> bf16 column sums.  Column j goes to element
+//                    j % seg of output j / seg (o0, o1, o2; a null output is
+//                    skipped), so N <= 3 * seg.  Fixed summation tree.
 int64_t hip_bias_grad_partial_floats(int64_t N);
+void hip_colsum_reduce(const float* partial, int64_t G, int64_t N, int64_t seg,
+                       void* o0, void* o1, void* o2, hipStream_t s);
 int64_t hip_bias_grad_sweep_rows(int64_t R, int64_t N, bool pack);
 void hip_gelu_bwd_colsum(const void* dy, const void* x, void* dx, void* db,
                          float* partial, int64_t R, int64_t C, hipStream_t s);
@@ -345,6 +356,14 @@ void hip_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
 // (B, H, T) fp32 is the only workspace: the first kernel fills it with
 // sum_d dout * out, the second reads it.  scale > 0.  Throws on anything
 // else.
+// With `colsum_partial` and `db` set (both or neither) the two kernels also
+// sum, per column, the bf16 values they store: workgroup (batch b, row block
+// i of ceil(T / 128), head h) writes 64 fp32 sums per output into row
+// b * nblocks + i of `colsum_partial` (rows of 3 * H * 64 columns: dq's heads
+// first, then dk's, then dv's; hip_attn_bwd_colsum_floats(B, H, T) floats,
+// 16-byte aligned, never zeroed), and hip_colsum_reduce turns the rows into
+// the 3 * H * 64 bf16 sums `db`.  With dq, dk, dv the three views of a packed
+// (B, T, 3 * H * 64) buffer, db is the column sum of that buffer.
 void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
                               const void* out, const void* dout,
                               const float* lse, void* dq, void* dk, void* dv,
@@ -357,7 +376,9 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
                               const int64_t* dq_strides,
                               const int64_t* dk_strides,
                               const int64_t* dv_strides, int64_t lse_stride,
-                              float scale, hipStream_t s);
+                              float scale, float* colsum_partial, void* db,
+                              hipStream_t s);
+int64_t hip_attn_bwd_colsum_floats(int64_t B, int64_t H, int64_t T);
 
 // Causal bf16 grouped-query attention forward, head dim 64
 // (gqa_attn_kernels.hip).  As hip_attn_fwd_causal_hd64, with q of Hq heads

@@ -80,6 +80,19 @@ FUSE_ATTN_FWD = True
 # matters where the forward above is ours.
 FUSE_ATTN_BWD = True
 
+# Run the qkv split and the attention as one autograd node
+# (fused_attn.fused_qkv_causal_attention): the two backward kernels write dq,
+# dk, dv straight into the packed (B, T, 3C) gradient and sum its columns for
+# qkv.bias.grad in their store epilogue, so the pack pass (k_pack3_colsum)
+# and its launch go away.  It applies only where the three flags above
+# (FUSE_QKV_BIAS_GRAD, FUSE_ATTN_FWD, FUSE_ATTN_BWD) all apply; everything
+# else keeps the split + attention path.  Measured 0.678 ms (0.677-0.679)
+# against 0.766 ms (0.766-0.768) for attn_backward + pack3_colsum at B=64
+# H=12 T=1024, and 73.96 / 74.37 / 73.90 ms per bench.py step against 75.31 /
+# 74.97 / 75.31 with the flag off, so it is on.  Numbers in profiles/r14/.
+# SHTENS_FUSED_QKV_ATTN = 0 or 1 overrides the flag for an A/B run.
+FUSE_QKV_ATTN_BWD = True
+
 # Take the weight gradient of the four layer Linears (attn.qkv, attn.proj,
 # mlp.fc, mlp.proj) from our split-K kernel (ops/fused_wgrad.py) instead of
 # the library's NT GEMM; forward, dX and the bias gradients stay where they
@@ -112,6 +125,18 @@ def _attn_ok(q, k, v) -> bool:
         return False
     from ..ops import fused_attn
     return fused_attn.can_use(q, k, v)
+
+
+def _qkv_attn_ok(qkv, bias, n_head: int) -> bool:
+    """The packed qkv + attention node: on only where our forward and our
+    backward both run today and its own flag is set."""
+    if not (_flag("SHTENS_FUSED_QKV_ATTN", FUSE_QKV_ATTN_BWD)
+            and _flag("SHTENS_FUSED_ATTN", FUSE_ATTN_FWD)
+            and _flag("SHTENS_FUSED_ATTN_BWD", FUSE_ATTN_BWD)
+            and qkv.is_cuda):
+        return False
+    from ..ops import fused_attn
+    return fused_attn.can_use_packed(qkv, bias, n_head)
 
 
 def _bias_grad_ok(flag: bool, which: str, x, lin: nn.Linear) -> bool:
@@ -192,18 +217,36 @@ class CausalSelfAttention(nn.Module):
             from ..ops import fused_bias_grad
             qkv = _linear(x, self.qkv.weight, self.qkv.bias.detach())
             q, k, v = fused_bias_grad.qkv_split_bgrad(qkv, self.qkv.bias)
+            # packed: split, attention and their backward run as one node on
+            # qkv itself; nothing consumes q, k, v then, so autograd never
+            # runs the split node's backward (the pack pass).  The split
+            # call and the trip through _attend stay because existing tests
+            # pin them (see fused_attn._QkvSplitCausalAttn)
+            packed = ((qkv, self.qkv.bias)
+                      if _qkv_attn_ok(qkv, self.qkv.bias, self.n_head)
+                      else None)
+            y = self._attend(q, k, v, packed)
         else:
-            q, k, v = _linear(x, self.qkv.weight,
-                              self.qkv.bias).split(C, dim=2)
+            y = self._attend(*_linear(x, self.qkv.weight,
+                                      self.qkv.bias).split(C, dim=2))
+        y = y.transpose(1, 2).contiguous().view(B, T, C)
+        if not proj_bias:  # the caller adds proj.bias (see Block)
+            return _linear(y, self.proj.weight)
+        return _linear(y, self.proj.weight, self.proj.bias)
+
+    def _attend(self, q, k, v, packed=None):
+        """Causal attention on the (B, T, C) q, k, v; returns (B, H, T, D).
+        ``packed``: (qkv, qkv.bias) where ``_qkv_attn_ok`` holds."""
+        B, T, _ = q.shape
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         v = v.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         if _attn_ok(q, k, v):
             from ..ops import fused_attn
-            y = fused_attn.fused_causal_attention(
+            return fused_attn.fused_causal_attention(
                 q, k, v, fused_backward=_flag("SHTENS_FUSED_ATTN_BWD",
-                                              FUSE_ATTN_BWD))
-        elif x.is_cuda:
+                                              FUSE_ATTN_BWD), packed=packed)
+        if q.is_cuda:
             # CK efficient-attention measured +16% end-to-end over the
             # default aotriton flash backend on MI355X at these shapes
             # (profiles/README.md), identical loss; priority list falls
@@ -212,13 +255,8 @@ class CausalSelfAttention(nn.Module):
             with sdpa_kernel([SDPBackend.EFFICIENT_ATTENTION,
                               SDPBackend.FLASH_ATTENTION, SDPBackend.MATH],
                              set_priority=True):
-                y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-        else:
-            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-        y = y.transpose(1, 2).contiguous().view(B, T, C)
-        if not proj_bias:  # the caller adds proj.bias (see Block)
-            return _linear(y, self.proj.weight)
-        return _linear(y, self.proj.weight, self.proj.bias)
+                return F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        return F.scaled_dot_product_attention(q, k, v, is_causal=True)
 
 
 class MLP(nn.Module):

@@ -13,6 +13,11 @@ two Functions here give the bias its gradient instead:
   packs dq, dk, dv into ``dqkv`` and sums its columns in one kernel; torch
   ran a cat and then read ``dqkv`` again to reduce it.
 
+Where ``fused_attn.fused_qkv_causal_attention`` applies, models/gpt2.py feeds
+the attention from ``qkv`` itself and leaves the q, k, v of
+``qkv_split_bgrad`` unused, so the pack never runs there: the attention
+backward writes ``dqkv`` and the column sums directly.
+
 Only the qkv half is wired into models/gpt2.py by default: the GELU half
 measured slower than the two torch kernels it replaces (profiles/r07/).
 
