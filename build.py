@@ -44,7 +44,7 @@ SOURCES = [
     "bindings.cpp",
 ]
 
-HEADERS = ["attn_bwd_tile.h", "common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
+HEADERS = ["attn_bwd_tile.h", "attn_fwd_tile.h", "attn_tile.h", "common.h", "codec_cpu.h", "device_util.h", "engine.h", "gelu_math.h", "hip_api.h",
            "optim_step.h", "rccl_transport.h"]
 
 

@@ -103,8 +103,9 @@
 namespace shamd {
 namespace {
 
-// The tile swizzle, the two LDS read patterns, grid_map and the staged
-// epilogue live in attn_bwd_tile.h, shared with gqa_attn_bwd_kernels.hip.
+// The tile swizzle, the two LDS read patterns, the staged epilogue, the dQ
+// body and the dK/dV half tile live in attn_bwd_tile.h, shared with
+// gqa_attn_bwd_kernels.hip.
 
 // ------------------------------------------------------------------ dQ
 
@@ -114,154 +115,28 @@ __global__ __launch_bounds__(256)
     const uint16_t* __restrict__ v, const uint16_t* __restrict__ out,
     const uint16_t* __restrict__ dout, const float* __restrict__ lse,
     uint16_t* __restrict__ dq, float* __restrict__ delta, int nbh, int H,
-    int T, int nqb, BwdStrides sq, BwdStrides sk, BwdStrides sv, BwdStrides so,
-    BwdStrides sdo, BwdStrides sdq, int64_t lse_stride, float scale,
-    float* __restrict__ csq, int64_t cs_ld) {
+    int T, int nqb, AttnStrides sq, AttnStrides sk, AttnStrides sv,
+    AttnStrides so, AttnStrides sdo, AttnStrides sdq, int64_t lse_stride,
+    float scale, float* __restrict__ csq, int64_t cs_ld) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * kTileBytes];
-  // K buffers at 0 and kTileBytes, V buffers behind them
-  unsigned char* const ldsK = lds;
-  unsigned char* const ldsV = lds + 2 * kTileBytes;
-
   int bh, slot;
   if (!grid_map(nbh, nqb, bh, slot)) return;  // whole workgroup
-  const int qb = nqb - 1 - slot;              // heaviest block first
-  const int b = bh / H, h = bh % H;
-
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int r = lane & 31, hi = lane >> 5;
-  const LaneOffs lo = lane_offs(lane);
-
-  const int q0 = qb * kRB;
-  const int qw0 = q0 + wave * kRW;  // the wave's first query row
-  const int qrow = qw0 + r;         // this lane's query row
-  const bool qok = qrow < T;
-
-  const uint16_t* qp = q + b * sq.b + h * sq.h + (int64_t)qrow * sq.t;
-  const uint16_t* op = out + b * so.b + h * so.h + (int64_t)qrow * so.t;
-  const uint16_t* dop = dout + b * sdo.b + h * sdo.h + (int64_t)qrow * sdo.t;
-  const uint16_t* kp = k + b * sk.b + h * sk.h;
-  const uint16_t* vp = v + b * sv.b + h * sv.h;
-
-  // Q and dO fragments: B operands; lane holds X[qrow][16 ks + 8 hi + j].
-  // delta from the same elements of dO and O.
-  bf16x8 qf[4], dof[4];
-  float dl = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const int d0 = 16 * ks + 8 * hi;
-    qf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(qp + d0, qok));
-    dof[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(dop + d0, qok));
-    bf16x8 of = __builtin_bit_cast(bf16x8, load16_or_zero(op + d0, qok));
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      dl = __builtin_fmaf((float)dof[ks][e], (float)of[e], dl);
-  }
-  dl += other_half(dl, lane);
-  if (hi == 0 && qok) delta[(int64_t)bh * T + qrow] = dl;
-  // -lse * log2(e); rows past T: any finite value, their dS is 0 * finite
-  const float nl = qok ? -lse[(int64_t)bh * lse_stride + qrow] * kLog2e : 0.f;
-  const float scale_log2e = scale * kLog2e;
-
-  // staging: thread covers 16-byte chunk (tid & 7) of keys (tid >> 3) and
-  // (tid >> 3) + 32 of the tile, for K and for V
-  const int skey = tid >> 3, sch = tid & 7;
-  u32x4 stK[2], stV[2];
-  auto issue = [&](int kv0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int key = kv0 + skey + 32 * i;
-      bool ok = key < T;
-      stK[i] = load16_or_zero(kp + (int64_t)key * sk.t + 8 * sch, ok);
-      stV[i] = load16_or_zero(vp + (int64_t)key * sv.t + 8 * sch, ok);
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int off = buf * kTileBytes + t_off(skey + 32 * i, sch);
-      *reinterpret_cast<u32x4*>(ldsK + off) = stK[i];
-      *reinterpret_cast<u32x4*>(ldsV + off) = stV[i];
-    }
-  };
-
-  const int kv_end = min(T, q0 + kRB);             // keys this block can see
-  const int ntiles = (kv_end + kTile - 1) / kTile;  // >= 1
-
-  f32x16 acc[2];  // dQ^T: lane holds dQ[qrow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
-
-  issue(0);
-  commit(0);
-  __syncthreads();
-
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
-    const int kv0 = t * kTile;
-    const bool more = t + 1 < ntiles;
-    if (more) issue(kv0 + kTile);
-
-    const unsigned char* Kt = ldsK + cur * kTileBytes;
-    const unsigned char* Vt = ldsV + cur * kTileBytes;
-    // keys of the tile are kv0 + 4 hi + c, c a register constant; key c is
-    // visible when c <= vis.  Tiles below the diagonal: everything.
-    const int vis = kv0 + kTile - 1 > qw0 ? qrow - kv0 - 4 * hi : kTile;
-
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      // wave-uniform: the half tile has keys the wave's rows can see
-      if (kv0 + 32 * kb > qw0 + kRW - 1) continue;
-
-      // S^T = K Q^T and dP^T = V dO^T for keys kv0 + 32 kb + keymap(reg, hi)
-      f32x16 s, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Kt, lo, kb, ks),
-                                                    qf[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vt, lo, kb, ks),
-                                                     dof[ks], dp, 0, 0, 0);
-      }
-
-      bf16x8 dsf[2];  // dS^T fragments: k-steps 2 kb and 2 kb + 1
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float p = __builtin_amdgcn_exp2f(
-            __builtin_fmaf(s[i], scale_log2e, nl));
-        if (32 * kb + (i & 3) + 8 * (i >> 2) > vis) p = 0.f;
-        dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl));
-      }
-
-      // dQ^T += K^T dS^T
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-          acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Kt, lo, 2 * kb + h2, nb), dsf[h2], acc[nb], 0, 0, 0);
-    }
-
-    if (more) commit(cur ^ 1);
-    __syncthreads();
-  }
-
-  // the loop's last barrier is behind every wave: the tiles are dead
-  unsigned char* const Ow = lds + wave * (kRW * 128);
-  stage_rows(Ow, acc, scale, r, hi);
-  __syncthreads();
-  uint16_t* const dqp = dq + b * sdq.b + h * sdq.h;
+  const DqRows w = attn_bwd_dq_body<1>(lds, bh, slot, q, k, v, out, dout, lse,
+                                       delta, H, 1, T, nqb, sq, sk, sv, so,
+                                       sdo, lse_stride, scale);
+  const int tid = threadIdx.x, lane = tid & 63;
+  uint16_t* const dqp = dq + w.b * sdq.b + w.h * sdq.h;
   if (!csq) {  // kernel argument: the whole workgroup takes one side
-    store_rows(Ow, dqp, sdq.t, qw0, T, lane);
+    store_rows(w.Ow, dqp, sdq.t, w.qw0, T, lane);
     return;
   }
   float cs[1][8];
-  store_rows_colsum(Ow, dqp, sdq.t, qw0, T, lane, cs[0]);
-  float* const part[1] = {csq + ((int64_t)b * nqb + qb) * cs_ld + h * kD};
-  colsum_partial_rows<1>(lds, kRW * 128, wave, tid, cs, part);
+  store_rows_colsum(w.Ow, dqp, sdq.t, w.qw0, T, lane, cs[0]);
+  float* const part[1] = {csq + ((int64_t)w.b * nqb + w.qb) * cs_ld +
+                          w.h * kD};
+  colsum_partial_rows<1>(lds, kRW * 128,
+                         __builtin_amdgcn_readfirstlane(tid >> 6), tid, cs,
+                         part);
 }
 
 // ------------------------------------------------------------- dK, dV
@@ -272,8 +147,8 @@ __global__ __launch_bounds__(256)
     const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int nbh, int H,
-    int T, int nkb, BwdStrides sq, BwdStrides sk, BwdStrides sv,
-    BwdStrides sdo, BwdStrides sdk, BwdStrides sdv, int64_t lse_stride,
+    int T, int nkb, AttnStrides sq, AttnStrides sk, AttnStrides sv,
+    AttnStrides sdo, AttnStrides sdk, AttnStrides sdv, int64_t lse_stride,
     float scale, float* __restrict__ csk, float* __restrict__ csv,
     int64_t cs_ld) {
   __shared__ __attribute__((aligned(16))) unsigned char
@@ -376,47 +251,8 @@ __global__ __launch_bounds__(256)
     for (int qh = 0; qh < 2; ++qh) {
       // wave-uniform: the half tile has queries that see the wave's keys
       if (qt0 + 32 * qh + 31 < kw0) continue;
-
-      // S = Q K^T and dP = dO V^T for queries qt0 + 32 qh + rowmap(reg, hi)
-      f32x16 s, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qt, lo, qh, ks),
-                                                    kf[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Dt, lo, qh, ks),
-                                                     vf[ks], dp, 0, 0, 0);
-      }
-
-      bf16x8 pf[2], dsf[2];  // P and dS fragments: k-steps 2 qh and 2 qh + 1
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        // registers 4 g .. 4 g + 3 are queries 32 qh + 8 g + 4 hi + 0..3
-        const int c0 = 32 * qh + 8 * g;
-        f32x4 nl4 = *reinterpret_cast<const f32x4*>(LD + c0 + 4 * hi);
-        f32x4 dl4 = *reinterpret_cast<const f32x4*>(LD + kTile + c0 + 4 * hi);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int i = 4 * g + e;
-          float p = __builtin_amdgcn_exp2f(
-              __builtin_fmaf(s[i], scale_log2e, nl4[e]));
-          if (c0 + e < need) p = 0.f;
-          pf[i >> 3][i & 7] = (__bf16)p;
-          dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl4[e]));
-        }
-      }
-
-      // dV^T += dO^T P, dK^T += Q^T dS
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          dva[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Dt, lo, 2 * qh + h2, nb), pf[h2], dva[nb], 0, 0, 0);
-          dka[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Qt, lo, 2 * qh + h2, nb), dsf[h2], dka[nb], 0, 0, 0);
-        }
+      dkdv_half_tile(Qt, Dt, LD, lo, qh, hi, need, scale_log2e, kf, vf, dka,
+                     dva);
     }
 
     if (more) commit(cur ^ 1);
@@ -461,60 +297,14 @@ void hip_attn_bwd_causal_hd64(const void* q, const void* k, const void* v,
     throw std::runtime_error(std::string(op) +
                              ": colsum_partial and db go together");
   check_align(colsum_partial, 16, op, "colsum_partial");
-  if (B <= 0 || H <= 0 || T <= 0)
-    throw std::runtime_error(std::string(op) + ": empty problem");
-  if (!(scale > 0.f) || scale > 3.0e38f)
-    throw std::runtime_error(std::string(op) + ": scale must be positive");
-  if (lse_stride < T)
-    throw std::runtime_error(std::string(op) + ": lse row shorter than T");
-  const void* ptrs[] = {q, k, v, out, dout, dq, dk, dv};
-  const char* names[] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
-  for (int i = 0; i < 8; ++i) {
-    if (!ptrs[i])
-      throw std::runtime_error(std::string(op) + ": " + names[i] + " is null");
-    check_align(ptrs[i], 16, op, names[i]);
-  }
-  if (!lse || !delta)
-    throw std::runtime_error(std::string(op) + ": lse or delta is null");
-  check_align(lse, 4, op, "lse");
-  check_align(delta, 4, op, "delta");
-  for (const int64_t* st : {qs, ks, vs, os, dos, dqs, dks, dvs})
-    for (int i = 0; i < 3; ++i)
-      if (st[i] < 0 || st[i] % 8)
-        throw std::runtime_error(std::string(op) +
-                                 ": strides must be multiples of 8 elements");
-  // no two output rows may overlap: with the dimensions of more than one
-  // element ordered by stride, the smallest stride covers a 64-element row
-  // and every further one the whole extent of the dimension before it
-  const int64_t dims[3] = {B, T, H};
-  for (const int64_t* st : {dqs, dks, dvs}) {
-    int64_t sd[3][2];
-    int n = 0;
-    for (int i = 0; i < 3; ++i)
-      if (dims[i] > 1) {
-        int j = n++;
-        for (; j > 0 && sd[j - 1][0] > st[i]; --j) {
-          sd[j][0] = sd[j - 1][0];
-          sd[j][1] = sd[j - 1][1];
-        }
-        sd[j][0] = st[i];
-        sd[j][1] = dims[i];
-      }
-    int64_t need = kD;
-    for (int i = 0; i < n; ++i) {
-      if (sd[i][0] < need)
-        throw std::runtime_error(std::string(op) +
-                                 ": output rows would overlap");
-      need = sd[i][0] * sd[i][1];
-    }
-  }
+  check_attn_bwd(op, q, k, v, out, dout, lse, dq, dk, dv, delta, B, H, H, T,
+                 qs, ks, vs, os, dos, dqs, dks, dvs, lse_stride, scale,
+                 /*grouped=*/false);
   const int64_t nblk = (T + kRB - 1) / kRB;
   const int64_t nbh = B * H;
   const int64_t C = H * kD;  // a partial row is [dq | dk | dv], C columns each
-  const int64_t grid = (nbh + kXcd - 1) / kXcd * kXcd * nblk;
-  if (grid > 0x7fffffff || T > (1 << 30) || nbh > 0x7fffffff)
-    throw std::runtime_error(std::string(op) + ": problem too large");
-  auto st3 = [](const int64_t* p) { return BwdStrides{p[0], p[1], p[2]}; };
+  const int64_t grid = attn_grid(op, B, H, H, T, nblk);
+  auto st3 = strides3;
   auto u16 = [](const void* p) { return static_cast<const uint16_t*>(p); };
   k_attn_bwd_dq<<<dim3((unsigned)grid), dim3(256), 0, s>>>(
       u16(q), u16(k), u16(v), u16(out), u16(dout), lse,

@@ -1,39 +1,22 @@
-// Tile helpers of the attention backward kernels for head dim 64, shared by
+// What the attention backward kernels for head dim 64 share,
 // attn_bwd_kernels.hip (MHA) and gqa_attn_bwd_kernels.hip (GQA): the LDS tile
 // swizzle, the two LDS read patterns that feed mfma_f32_32x32x16_bf16, the
-// workgroup-to-XCD grid map and the staged whole-row epilogue, with and
-// without the column sums of what it stores (MHA only).  The header
-// comment of attn_bwd_kernels.hip derives the swizzle and the lane layouts.
+// staged whole-row epilogue, with and without the column sums of what it
+// stores (MHA only), the dQ kernel up to its store (attn_bwd_dq_body; MHA is
+// its HW = 1, G = 1 case), the half tile of the dK/dV kernels
+// (dkdv_half_tile) and the launchers' argument checks.  The header comment
+// of attn_bwd_kernels.hip derives the swizzle and the lane layouts.
 // Everything sits in an anonymous namespace: each kernel file gets its own
 // copy, inlined.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "attn_tile.h"
 
 namespace shamd {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kD = 64;          // head dim
-constexpr int kRW = 32;         // rows (queries or keys) per wave
-constexpr int kWaves = 4;
-constexpr int kRB = kRW * kWaves;  // rows per workgroup
-constexpr int kTile = 64;       // rows per LDS tile
 constexpr int kTileBytes = kTile * kD * 2;
-constexpr int kXcd = 8;
-constexpr float kLog2e = 1.4426950408889634f;
-
-struct BwdStrides {
-  int64_t b, t, h;  // elements
-};
 
 // the chunk swizzle of a row: f((row >> 1) & 7)
 __device__ __forceinline__ int swz(int row) {
@@ -112,17 +95,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile,
     for (int e = 0; e < 4; ++e) f[4 * jj + e] = tb[e];
   }
   return f;
-}
-
-// blockIdx -> (batch*head, block slot): block ids round-robin over the XCDs,
-// the blocks of one (b, h) consecutive on one XCD
-__device__ __forceinline__ bool grid_map(int nbh, int nblk, int& bh,
-                                         int& slot_in_bh) {
-  const int xcd = blockIdx.x % kXcd;
-  const int slot = blockIdx.x / kXcd;
-  bh = (slot / nblk) * kXcd + xcd;
-  slot_in_bh = slot % nblk;
-  return bh < nbh;
 }
 
 // fp32 rows of a wave -> bf16 through the wave's 4 KB of LDS -> whole-row
@@ -231,6 +203,280 @@ __device__ __forceinline__ void colsum_partial_rows(unsigned char* lds,
       if (tid >= o * kD) d = dst[o];
     d[tid % kD] = t;
   }
+}
+
+// ------------------------------------------------------------------ dQ
+
+// What the store epilogue of a dQ kernel needs: the wave's batch, query head,
+// position block, first query row and its 4 KB of staged bf16 dQ rows.
+struct DqRows {
+  int b, h, qb, qw0;
+  unsigned char* Ow;
+};
+
+// A dQ kernel from its prologue through stage_rows and the barrier behind
+// it, for the workgroup of kv head `bk`, block slot `slot` (grid_map over
+// nqb * G / HW slots).  A wave is a query head: workgroup = 4 waves = HW heads
+// of one kv group x 128 / HW consecutive query positions.  lds: 4 tiles.
+// nqb = position blocks of 128 / HW rows.
+template <int HW>
+__device__ __forceinline__ DqRows attn_bwd_dq_body(
+    unsigned char* lds, int bk, int slot, const uint16_t* q,
+    const uint16_t* k, const uint16_t* v, const uint16_t* out,
+    const uint16_t* dout, const float* lse, float* delta, int Hkv, int G,
+    int T, int nqb, AttnStrides sq, AttnStrides sk, AttnStrides sv,
+    AttnStrides so, AttnStrides sdo, int64_t lse_stride, float scale) {
+  constexpr int kWPH = kWaves / HW;  // waves per head
+  constexpr int kPB = kRW * kWPH;    // positions per workgroup
+  // K buffers at 0 and kTileBytes, V buffers behind them
+  unsigned char* const ldsK = lds;
+  unsigned char* const ldsV = lds + 2 * kTileBytes;
+
+  const int nhalf = G / HW;
+  const int qb = nqb - 1 - slot / nhalf;  // heaviest block first
+  const int half = slot % nhalf;
+  const int b = bk / Hkv, kvh = bk % Hkv;
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int r = lane & 31, hi = lane >> 5;
+  const LaneOffs lo = lane_offs(lane);
+
+  const int Hq = Hkv * G;
+  const int h = G * kvh + HW * half + wave / kWPH;  // the wave's query head
+  const int64_t bh = (int64_t)b * Hq + h;
+  const int q0 = qb * kPB;
+  const int qw0 = q0 + (wave % kWPH) * kRW;  // the wave's first query row
+  const int qrow = qw0 + r;                  // this lane's query row
+  const bool qok = qrow < T;
+
+  const uint16_t* qp = q + b * sq.b + h * sq.h + (int64_t)qrow * sq.t;
+  const uint16_t* op = out + b * so.b + h * so.h + (int64_t)qrow * so.t;
+  const uint16_t* dop = dout + b * sdo.b + h * sdo.h + (int64_t)qrow * sdo.t;
+  const uint16_t* kp = k + b * sk.b + kvh * sk.h;
+  const uint16_t* vp = v + b * sv.b + kvh * sv.h;
+
+  // Q and dO fragments: B operands; lane holds X[qrow][16 ks + 8 hi + j].
+  // delta from the same elements of dO and O.
+  bf16x8 qf[4], dof[4];
+  float dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int d0 = 16 * ks + 8 * hi;
+    qf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(qp + d0, qok));
+    dof[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(dop + d0, qok));
+    bf16x8 of = __builtin_bit_cast(bf16x8, load16_or_zero(op + d0, qok));
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      dl = __builtin_fmaf((float)dof[ks][e], (float)of[e], dl);
+  }
+  dl += other_half(dl, lane);
+  if (hi == 0 && qok) delta[bh * T + qrow] = dl;
+  // -lse * log2(e); rows past T: any finite value, their dS is 0 * finite
+  const float nl = qok ? -lse[bh * lse_stride + qrow] * kLog2e : 0.f;
+  const float scale_log2e = scale * kLog2e;
+
+  // staging: thread covers 16-byte chunk (tid & 7) of keys (tid >> 3) and
+  // (tid >> 3) + 32 of the tile, for K and for V
+  const int skey = tid >> 3, sch = tid & 7;
+  u32x4 stK[2], stV[2];
+  auto issue = [&](int kv0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int key = kv0 + skey + 32 * i;
+      bool ok = key < T;
+      stK[i] = load16_or_zero(kp + (int64_t)key * sk.t + 8 * sch, ok);
+      stV[i] = load16_or_zero(vp + (int64_t)key * sv.t + 8 * sch, ok);
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int off = buf * kTileBytes + t_off(skey + 32 * i, sch);
+      *reinterpret_cast<u32x4*>(ldsK + off) = stK[i];
+      *reinterpret_cast<u32x4*>(ldsV + off) = stV[i];
+    }
+  };
+
+  const int kv_end = min(T, q0 + kPB);              // keys this block can see
+  const int ntiles = (kv_end + kTile - 1) / kTile;  // >= 1
+
+  f32x16 acc[2];  // dQ^T: lane holds dQ[qrow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
+
+  issue(0);
+  commit(0);
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int cur = t & 1;
+    const int kv0 = t * kTile;
+    const bool more = t + 1 < ntiles;
+    if (more) issue(kv0 + kTile);
+
+    const unsigned char* Kt = ldsK + cur * kTileBytes;
+    const unsigned char* Vt = ldsV + cur * kTileBytes;
+    // keys of the tile are kv0 + 4 hi + c, c a register constant; key c is
+    // visible when c <= vis.  Tiles below the diagonal: everything.
+    const int vis = kv0 + kTile - 1 > qw0 ? qrow - kv0 - 4 * hi : kTile;
+
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      // wave-uniform: the half tile has keys the wave's rows can see
+      if (kv0 + 32 * kb > qw0 + kRW - 1) continue;
+
+      // S^T = K Q^T and dP^T = V dO^T for keys kv0 + 32 kb + keymap(reg, hi)
+      f32x16 s, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Kt, lo, kb, ks),
+                                                    qf[ks], s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vt, lo, kb, ks),
+                                                     dof[ks], dp, 0, 0, 0);
+      }
+
+      bf16x8 dsf[2];  // dS^T fragments: k-steps 2 kb and 2 kb + 1
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float p = __builtin_amdgcn_exp2f(
+            __builtin_fmaf(s[i], scale_log2e, nl));
+        if (32 * kb + (i & 3) + 8 * (i >> 2) > vis) p = 0.f;
+        dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl));
+      }
+
+      // dQ^T += K^T dS^T
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+          acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(Kt, lo, 2 * kb + h2, nb), dsf[h2], acc[nb], 0, 0, 0);
+    }
+
+    if (more) commit(cur ^ 1);
+    __syncthreads();
+  }
+
+  // the loop's last barrier is behind every wave: the tiles are dead
+  unsigned char* const Ow = lds + wave * (kRW * 128);
+  stage_rows(Ow, acc, scale, r, hi);
+  __syncthreads();
+  return DqRows{b, h, qb, qw0, Ow};
+}
+
+// ------------------------------------------------------------- dK, dV
+
+// One 32-query half tile qh of a dK/dV kernel: S = Q K^T and dP = dO V^T for
+// queries 32 qh + rowmap(reg, hi) of the tile, P and dS per register, then
+// dV^T += dO^T P and dK^T += Q^T dS.  LD: the tile's 64 -lse log2(e) and 64
+// delta values, read as 16-byte broadcast reads.  Query c of the tile sees
+// the lane's key when c >= need.
+__device__ __forceinline__ void dkdv_half_tile(
+    const unsigned char* Qt, const unsigned char* Dt, const float* LD,
+    const LaneOffs& lo, int qh, int hi, int need, float scale_log2e,
+    const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], f32x16 (&dka)[2],
+    f32x16 (&dva)[2]) {
+  f32x16 s, dp;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qt, lo, qh, ks),
+                                                kf[ks], s, 0, 0, 0);
+    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Dt, lo, qh, ks),
+                                                 vf[ks], dp, 0, 0, 0);
+  }
+
+  bf16x8 pf[2], dsf[2];  // P and dS fragments: k-steps 2 qh and 2 qh + 1
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    // registers 4 g .. 4 g + 3 are queries 32 qh + 8 g + 4 hi + 0..3
+    const int c0 = 32 * qh + 8 * g;
+    f32x4 nl4 = *reinterpret_cast<const f32x4*>(LD + c0 + 4 * hi);
+    f32x4 dl4 = *reinterpret_cast<const f32x4*>(LD + kTile + c0 + 4 * hi);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 4 * g + e;
+      float p = __builtin_amdgcn_exp2f(
+          __builtin_fmaf(s[i], scale_log2e, nl4[e]));
+      if (c0 + e < need) p = 0.f;
+      pf[i >> 3][i & 7] = (__bf16)p;
+      dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl4[e]));
+    }
+  }
+
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2) {
+      dva[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          tr_frag(Dt, lo, 2 * qh + h2, nb), pf[h2], dva[nb], 0, 0, 0);
+      dka[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          tr_frag(Qt, lo, 2 * qh + h2, nb), dsf[h2], dka[nb], 0, 0, 0);
+    }
+}
+
+// ------------------------------------------------------------------ host
+
+// no two rows of a (B, T, H, 64) output may overlap: with the dimensions of
+// more than one element ordered by stride, the smallest stride covers a
+// 64-element row and every further one the whole extent of the dimension
+// before it
+inline bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H) {
+  const int64_t dims[3] = {B, T, H};
+  int64_t sd[3][2];
+  int n = 0;
+  for (int i = 0; i < 3; ++i)
+    if (dims[i] > 1) {
+      int j = n++;
+      for (; j > 0 && sd[j - 1][0] > st[i]; --j) {
+        sd[j][0] = sd[j - 1][0];
+        sd[j][1] = sd[j - 1][1];
+      }
+      sd[j][0] = st[i];
+      sd[j][1] = dims[i];
+    }
+  int64_t need = kD;
+  for (int i = 0; i < n; ++i) {
+    if (sd[i][0] < need) return false;
+    need = sd[i][0] * sd[i][1];
+  }
+  return true;
+}
+
+// The checks both backward launchers make before they size their grids;
+// returns G = Hq / Hkv.  The MHA op passes Hq == Hkv and grouped = false.
+inline int64_t check_attn_bwd(
+    const char* op, const void* q, const void* k, const void* v,
+    const void* out, const void* dout, const float* lse, const void* dq,
+    const void* dk, const void* dv, const float* delta, int64_t B, int64_t Hq,
+    int64_t Hkv, int64_t T, const int64_t* qs, const int64_t* ks,
+    const int64_t* vs, const int64_t* os, const int64_t* dos,
+    const int64_t* dqs, const int64_t* dks, const int64_t* dvs,
+    int64_t lse_stride, float scale, bool grouped) {
+  const int64_t G =
+      check_attn_problem(op, B, Hq, Hkv, T, lse_stride, scale, grouped);
+  const void* ptrs[] = {q, k, v, out, dout, dq, dk, dv};
+  const char* names[] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
+  for (int i = 0; i < 8; ++i) {
+    if (!ptrs[i])
+      throw std::runtime_error(std::string(op) + ": " + names[i] + " is null");
+    check_align(ptrs[i], 16, op, names[i]);
+  }
+  if (!lse || !delta)
+    throw std::runtime_error(std::string(op) + ": lse or delta is null");
+  check_align(lse, 4, op, "lse");
+  check_align(delta, 4, op, "delta");
+  check_attn_strides(op, {qs, ks, vs, os, dos, dqs, dks, dvs});
+  if (!rows_disjoint(dqs, B, T, Hq) || !rows_disjoint(dks, B, T, Hkv) ||
+      !rows_disjoint(dvs, B, T, Hkv))
+    throw std::runtime_error(std::string(op) + ": output rows would overlap");
+  return G;
 }
 
 }  // namespace

@@ -20,11 +20,8 @@
 //   forward: workgroup = 4 waves = HW heads of one kv group x 128 / HW
 //   consecutive query positions, HW = min(G, 4); G = 8 takes two workgroups
 //   (head halves) per kv head and position block.  One staged K/V tile feeds
-//   HW heads.  The per-wave code is k_attn_bwd_dq's: Q and dO in registers,
-//   K and V tiles double-buffered in LDS (2 x (8 + 8) KB, one barrier per
-//   tile), half tiles of 32 keys, dS^T never leaves registers, delta written
-//   to the workspace on the way.  Only the wave's q/out/dout/dq base, its
-//   head index for lse and delta and kv_end = min(T, q0 + 128 / HW) differ.
+//   HW heads.  The kernel is attn_bwd_dq_body<HW> (attn_bwd_tile.h), which
+//   k_attn_bwd_dq runs with HW = 1, G = 1, followed by the plain store.
 //   * Grid: the forward's (all workgroups of one (b, kv head) consecutive on
 //     one XCD, heaviest (last) position block first, head halves adjacent).
 //   * Resources: amdgpu_waves_per_eu(3, 3): at most 168 VGPRs, no AGPRs, no
@@ -42,7 +39,7 @@
 //     parity follows the flattened index, not the tile index (an odd tile
 //     count flips it at every head boundary).  The per-head pointers are
 //     wave-uniform scalar arithmetic.
-//   * The tile body is k_attn_bwd_dkdv's.
+//   * The half-tile arithmetic is k_attn_bwd_dkdv's (dkdv_half_tile).
 //   * dK is scaled and dK, dV rounded once in the epilogue, and staged
 //     through LDS to whole-row stores.
 //   * Grid: one workgroup per (b, kv head, key block), the key blocks of one
@@ -58,8 +55,8 @@
 //     line.
 //
 // As built: k_gqa_bwd_dq_hd64<2> and <4> 154 VGPRs each (k_attn_bwd_dq:
-// 154), k_gqa_bwd_dkdv_hd64 194 VGPRs and 76 SGPRs (k_attn_bwd_dkdv: 198 and
-// 62: the per-head pointers went to scalar registers); no AGPRs, scratch or
+// 156), k_gqa_bwd_dkdv_hd64 194 VGPRs and 76 SGPRs (k_attn_bwd_dkdv: 198 and
+// 68: the per-head pointers went to scalar registers); no AGPRs, scratch or
 // spills.  No deviation from the plan.
 //
 // Every T is bounds-checked: rows at or past T are read as zeros (never from
@@ -83,153 +80,17 @@ __global__ __launch_bounds__(256)
     const uint16_t* __restrict__ v, const uint16_t* __restrict__ out,
     const uint16_t* __restrict__ dout, const float* __restrict__ lse,
     uint16_t* __restrict__ dq, float* __restrict__ delta, int nbk, int Hkv,
-    int G, int T, int nqb, BwdStrides sq, BwdStrides sk, BwdStrides sv,
-    BwdStrides so, BwdStrides sdo, BwdStrides sdq, int64_t lse_stride,
+    int G, int T, int nqb, AttnStrides sq, AttnStrides sk, AttnStrides sv,
+    AttnStrides so, AttnStrides sdo, AttnStrides sdq, int64_t lse_stride,
     float scale) {
-  constexpr int kWPH = kWaves / HW;  // waves per head
-  constexpr int kPB = kRW * kWPH;    // positions per workgroup
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * kTileBytes];
-  // K buffers at 0 and kTileBytes, V buffers behind them
-  unsigned char* const ldsK = lds;
-  unsigned char* const ldsV = lds + 2 * kTileBytes;
-
-  const int nhalf = G / HW;
   int bk, slot;
-  if (!grid_map(nbk, nqb * nhalf, bk, slot)) return;  // whole workgroup
-  const int qb = nqb - 1 - slot / nhalf;              // heaviest block first
-  const int half = slot % nhalf;
-  const int b = bk / Hkv, kvh = bk % Hkv;
-
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int r = lane & 31, hi = lane >> 5;
-  const LaneOffs lo = lane_offs(lane);
-
-  const int Hq = Hkv * G;
-  const int h = G * kvh + HW * half + wave / kWPH;  // the wave's query head
-  const int64_t bh = (int64_t)b * Hq + h;
-  const int q0 = qb * kPB;
-  const int qw0 = q0 + (wave % kWPH) * kRW;  // the wave's first query row
-  const int qrow = qw0 + r;                  // this lane's query row
-  const bool qok = qrow < T;
-
-  const uint16_t* qp = q + b * sq.b + h * sq.h + (int64_t)qrow * sq.t;
-  const uint16_t* op = out + b * so.b + h * so.h + (int64_t)qrow * so.t;
-  const uint16_t* dop = dout + b * sdo.b + h * sdo.h + (int64_t)qrow * sdo.t;
-  const uint16_t* kp = k + b * sk.b + kvh * sk.h;
-  const uint16_t* vp = v + b * sv.b + kvh * sv.h;
-
-  // Q and dO fragments: B operands; lane holds X[qrow][16 ks + 8 hi + j].
-  // delta from the same elements of dO and O.
-  bf16x8 qf[4], dof[4];
-  float dl = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const int d0 = 16 * ks + 8 * hi;
-    qf[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(qp + d0, qok));
-    dof[ks] = __builtin_bit_cast(bf16x8, load16_or_zero(dop + d0, qok));
-    bf16x8 of = __builtin_bit_cast(bf16x8, load16_or_zero(op + d0, qok));
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      dl = __builtin_fmaf((float)dof[ks][e], (float)of[e], dl);
-  }
-  dl += other_half(dl, lane);
-  if (hi == 0 && qok) delta[bh * T + qrow] = dl;
-  // -lse * log2(e); rows past T: any finite value, their dS is 0 * finite
-  const float nl = qok ? -lse[bh * lse_stride + qrow] * kLog2e : 0.f;
-  const float scale_log2e = scale * kLog2e;
-
-  // staging: thread covers 16-byte chunk (tid & 7) of keys (tid >> 3) and
-  // (tid >> 3) + 32 of the tile, for K and for V
-  const int skey = tid >> 3, sch = tid & 7;
-  u32x4 stK[2], stV[2];
-  auto issue = [&](int kv0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int key = kv0 + skey + 32 * i;
-      bool ok = key < T;
-      stK[i] = load16_or_zero(kp + (int64_t)key * sk.t + 8 * sch, ok);
-      stV[i] = load16_or_zero(vp + (int64_t)key * sv.t + 8 * sch, ok);
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int off = buf * kTileBytes + t_off(skey + 32 * i, sch);
-      *reinterpret_cast<u32x4*>(ldsK + off) = stK[i];
-      *reinterpret_cast<u32x4*>(ldsV + off) = stV[i];
-    }
-  };
-
-  const int kv_end = min(T, q0 + kPB);              // keys this block can see
-  const int ntiles = (kv_end + kTile - 1) / kTile;  // >= 1
-
-  f32x16 acc[2];  // dQ^T: lane holds dQ[qrow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
-
-  issue(0);
-  commit(0);
-  __syncthreads();
-
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
-    const int kv0 = t * kTile;
-    const bool more = t + 1 < ntiles;
-    if (more) issue(kv0 + kTile);
-
-    const unsigned char* Kt = ldsK + cur * kTileBytes;
-    const unsigned char* Vt = ldsV + cur * kTileBytes;
-    // keys of the tile are kv0 + 4 hi + c, c a register constant; key c is
-    // visible when c <= vis.  Tiles below the diagonal: everything.
-    const int vis = kv0 + kTile - 1 > qw0 ? qrow - kv0 - 4 * hi : kTile;
-
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      // wave-uniform: the half tile has keys the wave's rows can see
-      if (kv0 + 32 * kb > qw0 + kRW - 1) continue;
-
-      // S^T = K Q^T and dP^T = V dO^T for keys kv0 + 32 kb + keymap(reg, hi)
-      f32x16 s, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Kt, lo, kb, ks),
-                                                    qf[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vt, lo, kb, ks),
-                                                     dof[ks], dp, 0, 0, 0);
-      }
-
-      bf16x8 dsf[2];  // dS^T fragments: k-steps 2 kb and 2 kb + 1
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float p = __builtin_amdgcn_exp2f(
-            __builtin_fmaf(s[i], scale_log2e, nl));
-        if (32 * kb + (i & 3) + 8 * (i >> 2) > vis) p = 0.f;
-        dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl));
-      }
-
-      // dQ^T += K^T dS^T
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-          acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Kt, lo, 2 * kb + h2, nb), dsf[h2], acc[nb], 0, 0, 0);
-    }
-
-    if (more) commit(cur ^ 1);
-    __syncthreads();
-  }
-
-  // the loop's last barrier is behind every wave: the tiles are dead
-  unsigned char* const Ow = lds + wave * (kRW * 128);
-  stage_rows(Ow, acc, scale, r, hi);
-  __syncthreads();
-  store_rows(Ow, dq + b * sdq.b + h * sdq.h, sdq.t, qw0, T, lane);
+  if (!grid_map(nbk, nqb * (G / HW), bk, slot)) return;  // whole workgroup
+  const DqRows w = attn_bwd_dq_body<HW>(lds, bk, slot, q, k, v, out, dout, lse,
+                                        delta, Hkv, G, T, nqb, sq, sk, sv, so,
+                                        sdo, lse_stride, scale);
+  store_rows(w.Ow, dq + w.b * sdq.b + w.h * sdq.h, sdq.t, w.qw0, T,
+             threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------- dK, dV
@@ -241,8 +102,8 @@ __global__ __launch_bounds__(256)
     const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int nbk, int Hkv,
-    int G, int T, int nkb, BwdStrides sq, BwdStrides sk, BwdStrides sv,
-    BwdStrides sdo, BwdStrides sdk, BwdStrides sdv, int64_t lse_stride,
+    int G, int T, int nkb, AttnStrides sq, AttnStrides sk, AttnStrides sv,
+    AttnStrides sdo, AttnStrides sdk, AttnStrides sdv, int64_t lse_stride,
     float scale) {
   __shared__ __attribute__((aligned(16))) unsigned char
       lds[4 * kTileBytes + 2 * 2 * kTile * 4];
@@ -360,47 +221,8 @@ __global__ __launch_bounds__(256)
     for (int qh = 0; qh < 2; ++qh) {
       // wave-uniform: the half tile has queries that see the wave's keys
       if (qt0 + 32 * qh + 31 < kw0) continue;
-
-      // S = Q K^T and dP = dO V^T for queries qt0 + 32 qh + rowmap(reg, hi)
-      f32x16 s, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qt, lo, qh, ks),
-                                                    kf[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Dt, lo, qh, ks),
-                                                     vf[ks], dp, 0, 0, 0);
-      }
-
-      bf16x8 pf[2], dsf[2];  // P and dS fragments: k-steps 2 qh and 2 qh + 1
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        // registers 4 g4 .. 4 g4 + 3 are queries 32 qh + 8 g4 + 4 hi + 0..3
-        const int c0 = 32 * qh + 8 * g4;
-        f32x4 nl4 = *reinterpret_cast<const f32x4*>(LD + c0 + 4 * hi);
-        f32x4 dl4 = *reinterpret_cast<const f32x4*>(LD + kTile + c0 + 4 * hi);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int i = 4 * g4 + e;
-          float p = __builtin_amdgcn_exp2f(
-              __builtin_fmaf(s[i], scale_log2e, nl4[e]));
-          if (c0 + e < need) p = 0.f;
-          pf[i >> 3][i & 7] = (__bf16)p;
-          dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - dl4[e]));
-        }
-      }
-
-      // dV^T += dO^T P, dK^T += Q^T dS
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          dva[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Dt, lo, 2 * qh + h2, nb), pf[h2], dva[nb], 0, 0, 0);
-          dka[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              tr_frag(Qt, lo, 2 * qh + h2, nb), dsf[h2], dka[nb], 0, 0, 0);
-        }
+      dkdv_half_tile(Qt, Dt, LD, lo, qh, hi, need, scale_log2e, kf, vf, dka,
+                     dva);
     }
 
     if (more) commit(cur ^ 1);
@@ -417,32 +239,6 @@ __global__ __launch_bounds__(256)
   store_rows(Ow + kRW * 128, dv + b * sdv.b + kvh * sdv.h, sdv.t, kw0, T, lane);
 }
 
-// no two rows of a (B, T, H, 64) output may overlap: with the dimensions of
-// more than one element ordered by stride, the smallest stride covers a
-// 64-element row and every further one the whole extent of the dimension
-// before it
-bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H) {
-  const int64_t dims[3] = {B, T, H};
-  int64_t sd[3][2];
-  int n = 0;
-  for (int i = 0; i < 3; ++i)
-    if (dims[i] > 1) {
-      int j = n++;
-      for (; j > 0 && sd[j - 1][0] > st[i]; --j) {
-        sd[j][0] = sd[j - 1][0];
-        sd[j][1] = sd[j - 1][1];
-      }
-      sd[j][0] = st[i];
-      sd[j][1] = dims[i];
-    }
-  int64_t need = kD;
-  for (int i = 0; i < n; ++i) {
-    if (sd[i][0] < need) return false;
-    need = sd[i][0] * sd[i][1];
-  }
-  return true;
-}
-
 }  // namespace
 
 void hip_gqa_attn_bwd_causal_hd64(
@@ -454,48 +250,18 @@ void hip_gqa_attn_bwd_causal_hd64(
     const int64_t* dks, const int64_t* dvs, int64_t lse_stride, float scale,
     hipStream_t s) {
   const char* op = "gqa_attn_bwd_causal_hd64";
-  if (B <= 0 || Hq <= 0 || Hkv <= 0 || T <= 0)
-    throw std::runtime_error(std::string(op) + ": empty problem");
-  if (Hq % Hkv)
-    throw std::runtime_error(std::string(op) +
-                             ": Hq must be a multiple of Hkv");
-  const int64_t G = Hq / Hkv;
-  if (G != 2 && G != 4 && G != 8)
-    throw std::runtime_error(std::string(op) + ": group size must be 2, 4 or 8");
-  if (!(scale > 0.f) || scale > 3.0e38f)
-    throw std::runtime_error(std::string(op) + ": scale must be positive");
-  if (lse_stride < T)
-    throw std::runtime_error(std::string(op) + ": lse row shorter than T");
-  const void* ptrs[] = {q, k, v, out, dout, dq, dk, dv};
-  const char* names[] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
-  for (int i = 0; i < 8; ++i) {
-    if (!ptrs[i])
-      throw std::runtime_error(std::string(op) + ": " + names[i] + " is null");
-    check_align(ptrs[i], 16, op, names[i]);
-  }
-  if (!lse || !delta)
-    throw std::runtime_error(std::string(op) + ": lse or delta is null");
-  check_align(lse, 4, op, "lse");
-  check_align(delta, 4, op, "delta");
-  for (const int64_t* st : {qs, ks, vs, os, dos, dqs, dks, dvs})
-    for (int i = 0; i < 3; ++i)
-      if (st[i] < 0 || st[i] % 8)
-        throw std::runtime_error(std::string(op) +
-                                 ": strides must be multiples of 8 elements");
-  if (!rows_disjoint(dqs, B, T, Hq) || !rows_disjoint(dks, B, T, Hkv) ||
-      !rows_disjoint(dvs, B, T, Hkv))
-    throw std::runtime_error(std::string(op) + ": output rows would overlap");
+  const int64_t G = check_attn_bwd(op, q, k, v, out, dout, lse, dq, dk, dv,
+                                   delta, B, Hq, Hkv, T, qs, ks, vs, os, dos,
+                                   dqs, dks, dvs, lse_stride, scale,
+                                   /*grouped=*/true);
   const int HW = G < 4 ? 2 : 4;
   const int64_t pb = kRB / HW;
   const int64_t nqb = (T + pb - 1) / pb;
   const int64_t nkb = (T + kRB - 1) / kRB;
   const int64_t nbk = B * Hkv;
-  const int64_t nbk8 = (nbk + kXcd - 1) / kXcd * kXcd;
-  const int64_t grid_dq = nbk8 * nqb * (G / HW);
-  const int64_t grid_kv = nbk8 * nkb;
-  if (grid_dq > 0x7fffffff || T > (1 << 30) || B * Hq > 0x7fffffff)
-    throw std::runtime_error(std::string(op) + ": problem too large");
-  auto st3 = [](const int64_t* p) { return BwdStrides{p[0], p[1], p[2]}; };
+  const int64_t grid_dq = attn_grid(op, B, Hq, Hkv, T, nqb * (G / HW));
+  const int64_t grid_kv = attn_grid(op, B, Hq, Hkv, T, nkb);
+  auto st3 = strides3;
   auto u16 = [](const void* p) { return static_cast<const uint16_t*>(p); };
   auto launch_dq = [&](auto kern) {
     kern<<<dim3((unsigned)grid_dq), dim3(256), 0, s>>>(

@@ -17,344 +17,56 @@
 //     and workgroup count equal those of MHA with Hq heads.  With HW = 4
 //     every wave has the same causal extent: no wave idles through the
 //     barriers of tiles above its rows.
-//   * The per-wave code is attn_kernels.hip's: 32 rows per wave, Q in
-//     registers, 64-key tiles double-buffered in LDS (2 x (8 + 8) KB, one
-//     barrier per tile), the same K and V swizzles, S^T = mfma_32x32x16(K, Q)
-//     and O^T += mfma_32x32x16(V^T, P^T) with the transposed V read, so P
-//     never leaves registers, the same wave-uniform skip and mask conditions
-//     on the wave's own first row qw0.  Only the wave's q/out base, its head
-//     index for lse and kv_end = min(T, q0 + 128 / HW) differ.
-//   * out is contiguous (B, T, Hq, 64), lse (B, Hq, lse_stride >= T).
-//   * Grid: all workgroups of one (b, kv head) consecutive on one XCD
-//     (blockIdx % 8), heaviest (last) position block first, the two head
-//     halves of G = 8 adjacent, so K/V are re-read from that XCD's L2.
+//   * The per-wave code, the tiles, the grid map and the bounds checks are
+//     the forward body's, described once in attn_fwd_tile.h; this file is
+//     its <64, HW> case.
 //   * Resources: amdgpu_waves_per_eu(4, 4): at most 128 VGPRs (128 as built
-//     for HW = 2 and HW = 4, 37 SGPRs), no AGPRs, no scratch, no spills,
-//     32 KB of LDS -> 4 waves/SIMD, the MHA forward's line.  No deviation
-//     from the plan.
+//     for HW = 2 and HW = 4), no AGPRs, no scratch, no spills, 32 KB of LDS
+//     -> 4 waves/SIMD, the MHA forward's line.  No deviation from the plan.
 //
 // Whether this mapping is faster than the MHA kernel on expanded K/V rests
 // on the argument above until benchmarks/bench_model_kernels.py has measured
 // it (profiles/r12/).
-//
-// Every T is bounds-checked: query rows and key rows at or past T are read
-// as zeros (never from memory) and never stored.
 #include <hip/hip_runtime.h>
 
+#include "attn_fwd_tile.h"
 #include "device_util.h"
 #include "hip_api.h"
 
 namespace shamd {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kD = 64;         // head dim
-constexpr int kQW = 32;        // query rows per wave
-constexpr int kWaves = 4;
-constexpr int kKV = 64;        // keys per tile
-constexpr int kTileBytes = kKV * kD * 2;
-constexpr int kXcd = 8;
-
-struct GqaStrides {
-  int64_t b, t, h;  // elements
-};
-
-// The forward's helpers, copied from attn_kernels.hip (20 lines).
-// byte offset of 16-byte chunk `ch` (0..7) of key row `row` in a K tile
-__device__ __forceinline__ int k_off(int row, int ch) {
-  return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4);
-}
-// the same for a V tile
-__device__ __forceinline__ int v_off(int row, int ch) {
-  return row * 128 + ((ch ^ (((row >> 1) & 1) << 2)) << 4);
-}
-
-__device__ __forceinline__ uint4 load16_or_zero(const uint16_t* p, bool ok) {
-  uint4 z = make_uint4(0, 0, 0, 0);
-  return ok ? *reinterpret_cast<const uint4*>(p) : z;
-}
-
-// the other lane half's value (lane ^ 32)
-__device__ __forceinline__ float other_half(float x) {
-  return __shfl_xor(x, 32, 64);
-}
-
-// nbk = B * Hkv, nqb = position blocks of 128 / HW rows, nhalf = G / HW
+// nbk = B * Hkv, nqb = position blocks of 128 / HW rows
 template <int HW>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(4, 4))) void k_gqa_fwd_hd64(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
     const uint16_t* __restrict__ v, uint16_t* __restrict__ out,
     float* __restrict__ lse, int nbk, int Hkv, int G, int T, int nqb,
-    GqaStrides sq, GqaStrides sk, GqaStrides sv, int64_t lse_stride,
+    AttnStrides sq, AttnStrides sk, AttnStrides sv, int64_t lse_stride,
     float scale_log2e) {
-  constexpr int kWPH = kWaves / HW;   // waves per head
-  constexpr int kPB = kQW * kWPH;     // positions per workgroup
-  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * kTileBytes];
-  // K buffers at 0 and kTileBytes, V buffers behind them
-  unsigned char* const ldsK = lds;
-  unsigned char* const ldsV = lds + 2 * kTileBytes;
-
-  // blockIdx -> (kv head, position block, head half): block ids round-robin
-  // over the XCDs
-  const int nhalf = G / HW;
-  const int nblk = nqb * nhalf;
-  const int xcd = blockIdx.x % kXcd;
-  const int slot = blockIdx.x / kXcd;
-  const int bk = (slot / nblk) * kXcd + xcd;
-  if (bk >= nbk) return;  // whole workgroup, before any barrier
-  const int sl = slot % nblk;
-  const int qb = nqb - 1 - sl / nhalf;
-  const int half = sl % nhalf;
-  const int b = bk / Hkv, kvh = bk % Hkv;
-
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int r = lane & 31, hi = lane >> 5;
-
-  const int Hq = Hkv * G;
-  const int h = G * kvh + HW * half + wave / kWPH;  // the wave's query head
-  const int q0 = qb * kPB;
-  const int qw0 = q0 + (wave % kWPH) * kQW;  // the wave's first query row
-  const int qrow = qw0 + r;                  // this lane's query row
-
-  const uint16_t* qp = q + b * sq.b + h * sq.h;
-  const uint16_t* kp = k + b * sk.b + kvh * sk.h;
-  const uint16_t* vp = v + b * sv.b + kvh * sv.h;
-
-  // Q fragment: B operand of mfma(K, Q); lane holds Q[qrow][16 ks + 8 hi + j]
-  bf16x8 qf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    uint4 t = load16_or_zero(qp + (int64_t)qrow * sq.t + 16 * ks + 8 * hi,
-                             qrow < T);
-    qf[ks] = __builtin_bit_cast(bf16x8, t);
-  }
-
-  // staging: thread covers 16-byte chunk (tid & 7) of keys (tid >> 3) and
-  // (tid >> 3) + 32 of the tile, for K and for V
-  const int skey = tid >> 3, sch = tid & 7;
-  uint4 stK[2], stV[2];
-  auto issue = [&](int kv0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int key = kv0 + skey + 32 * i;
-      bool ok = key < T;
-      stK[i] = load16_or_zero(kp + (int64_t)key * sk.t + 8 * sch, ok);
-      stV[i] = load16_or_zero(vp + (int64_t)key * sv.t + 8 * sch, ok);
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int row = skey + 32 * i;
-      *reinterpret_cast<uint4*>(ldsK + buf * kTileBytes + k_off(row, sch)) =
-          stK[i];
-      *reinterpret_cast<uint4*>(ldsV + buf * kTileBytes + v_off(row, sch)) =
-          stV[i];
-    }
-  };
-
-  const int kv_end = min(T, q0 + kPB);          // keys this block can see
-  const int ntiles = (kv_end + kKV - 1) / kKV;  // >= 1
-
-  f32x16 o[2];  // O^T: lane holds O[qrow][32 nb + (reg&3) + 8 (reg>>2) + 4 hi]
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[nb][i] = 0.f;
-  float m = -INFINITY;  // running max of score * scale * log2(e)
-  float l = 0.f;        // this lane half's share of the running sum
-
-  // transposed-read address of V inside a tile, without the (s, jj, nb) part:
-  // 16-lane group g reads rows k0 .. k0+3, columns 32 nb + 16 (g & 1) + 0..15;
-  // lane 4 qq + p of the group supplies row qq, columns 4 p .. 4 p + 3
-  const int grp = lane >> 4, gi = lane & 15;
-  const int tr_q = gi >> 2, tr_p = gi & 3;
-
-  issue(0);
-  commit(0);
-  __syncthreads();
-
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
-    const int kv0 = t * kKV;
-    const bool more = t + 1 < ntiles;
-    if (more) issue(kv0 + kKV);
-
-    if (kv0 <= qw0 + kQW - 1) {  // wave-uniform: the tile has visible keys
-      const unsigned char* Kt = ldsK + cur * kTileBytes;
-      const unsigned char* Vt = ldsV + cur * kTileBytes;
-
-      // S^T = K Q^T: s[kb][reg] = score(qrow, kv0 + 32 kb + keymap(reg, hi))
-      f32x16 s[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          uint4 kk = *reinterpret_cast<const uint4*>(
-              Kt + k_off(32 * kb + r, 2 * ks + hi));
-          s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              __builtin_bit_cast(bf16x8, kk), qf[ks], s[kb], 0, 0, 0);
-        }
-      }
-
-      if (kv0 + kKV - 1 > qw0) {  // wave-uniform: the tile crosses the diagonal
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            int key = kv0 + 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * hi;
-            if (key > qrow) s[kb][i] = -INFINITY;
-          }
-      }
-
-      // every row has a visible key in every tile its wave processes, so the
-      // new max is finite and exp2(-inf - m) is a clean 0
-      float mx = s[0][0];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[kb][i]);
-      mx = fmaxf(mx, other_half(mx));
-      const float mn = fmaxf(m, mx * scale_log2e);
-      const float alpha = __builtin_amdgcn_exp2f(m - mn);
-      m = mn;
-
-      float rs = 0.f;
-      bf16x8 pf[4];  // P^T fragments: k-step ss = 2 kb + half of the regs
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          float p = __builtin_amdgcn_exp2f(
-              __builtin_fmaf(s[kb][i], scale_log2e, -mn));
-          rs += p;
-          pf[2 * kb + (i >> 3)][i & 7] = (__bf16)p;
-        }
-      l = l * alpha + rs;
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[nb][i] *= alpha;
-
-      // O^T += V^T P^T; element j of the fragment of k-step ss is key
-      // 16 ss + 8 (j >> 2) + 4 hi + (j & 3), the order P's registers have
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-#pragma unroll
-        for (int ss = 0; ss < 4; ++ss) {
-          bf16x8 vf;
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            int row = 16 * ss + 8 * jj + 4 * (grp >> 1) + tr_q;
-            int ch = 4 * nb + 2 * (grp & 1) + (tr_p >> 1);
-            auto* a = reinterpret_cast<
-                __attribute__((address_space(3))) s16x4*>(
-                (uintptr_t)(Vt + v_off(row, ch) + 8 * (tr_p & 1)));
-            s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a);
-            bf16x4 tb = __builtin_bit_cast(bf16x4, tr);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vf[4 * jj + e] = tb[e];
-          }
-          o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ss], o[nb], 0,
-                                                          0, 0);
-        }
-      }
-    }
-
-    if (more) commit(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---- epilogue: normalise, lse, O through LDS to whole-row stores
-  l += other_half(l);
-  const float inv = 1.f / l;
-  if (hi == 0 && qrow < T)
-    lse[((int64_t)b * Hq + h) * lse_stride + qrow] =
-        (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
-
-  // the loop's last barrier is behind every wave: K/V tiles are dead.  Each
-  // wave owns 4 KB: [32 rows][8 chunks of 16 B], chunks swizzled like K.
-  unsigned char* const Ow = lds + wave * (kQW * 128);
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float f[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) f[e] = o[nb][4 * g + e] * inv;
-      // d = 32 nb + 8 g + 4 hi + e: chunk 4 nb + g, its half hi
-      *reinterpret_cast<uint2*>(Ow + k_off(r, 4 * nb + g) + 8 * hi) = pack4(f);
-    }
-  __syncthreads();
-  uint16_t* op = out + ((int64_t)b * T * Hq + h) * kD;
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    int row = pass * 8 + (lane >> 3), ch = lane & 7;
-    uint4 val = *reinterpret_cast<const uint4*>(Ow + k_off(row, ch));
-    int qr = qw0 + row;
-    if (qr < T)
-      *reinterpret_cast<uint4*>(op + (int64_t)qr * Hq * kD + 8 * ch) = val;
-  }
+  attn_fwd_body<64, HW>(q, k, v, out, lse, nbk, Hkv, G, T, nqb, sq, sk,
+                        sv, lse_stride, scale_log2e);
 }
 
 }  // namespace
 
-void hip_gqa_attn_fwd_causal_hd64(const void* q, const void* k, const void* v,
-                                  void* out, float* lse, int64_t B, int64_t Hq,
-                                  int64_t Hkv, int64_t T, const int64_t* qs,
-                                  const int64_t* ks, const int64_t* vs,
-                                  int64_t lse_stride, float scale,
-                                  hipStream_t s) {
-  const char* op = "gqa_attn_fwd_causal_hd64";
-  if (B <= 0 || Hq <= 0 || Hkv <= 0 || T <= 0)
-    throw std::runtime_error(std::string(op) + ": empty problem");
-  if (Hq % Hkv)
-    throw std::runtime_error(std::string(op) +
-                             ": Hq must be a multiple of Hkv");
-  const int64_t G = Hq / Hkv;
-  if (G != 2 && G != 4 && G != 8)
-    throw std::runtime_error(std::string(op) + ": group size must be 2, 4 or 8");
-  if (!(scale > 0.f) || scale > 3.0e38f)
-    throw std::runtime_error(std::string(op) + ": scale must be positive");
-  if (lse_stride < T)
-    throw std::runtime_error(std::string(op) + ": lse row shorter than T");
-  if (!q || !k || !v || !out || !lse)
-    throw std::runtime_error(std::string(op) + ": null pointer");
-  check_align(q, 16, op, "q");
-  check_align(k, 16, op, "k");
-  check_align(v, 16, op, "v");
-  check_align(out, 16, op, "out");
-  check_align(lse, 4, op, "lse");
-  for (const int64_t* st : {qs, ks, vs})
-    for (int i = 0; i < 3; ++i)
-      if (st[i] < 0 || st[i] % 8)
-        throw std::runtime_error(std::string(op) +
-                                 ": strides must be multiples of 8 elements");
-  const int HW = G < 4 ? 2 : 4;
-  const int64_t pb = kQW * kWaves / HW;
-  const int64_t nqb = (T + pb - 1) / pb;
-  const int64_t nbk = B * Hkv;
-  const int64_t grid = (nbk + kXcd - 1) / kXcd * kXcd * nqb * (G / HW);
-  if (grid > 0x7fffffff || T > (1 << 30) || B * Hq > 0x7fffffff)
-    throw std::runtime_error(std::string(op) + ": problem too large");
-  GqaStrides a{qs[0], qs[1], qs[2]}, bb{ks[0], ks[1], ks[2]},
-      c{vs[0], vs[1], vs[2]};
+void hip_gqa_attn_fwd_causal_hd64(
+    const void* q, const void* k, const void* v, void* out, float* lse,
+    int64_t B, int64_t Hq, int64_t Hkv, int64_t T, const int64_t* qs,
+    const int64_t* ks, const int64_t* vs, int64_t lse_stride, float scale,
+    hipStream_t s) {
+  const FwdLaunch p =
+      check_attn_fwd("gqa_attn_fwd_causal_hd64", q, k, v, out, lse, B, Hq, Hkv, T, qs, ks, vs,
+                     lse_stride, scale, /*grouped=*/true);
   auto launch = [&](auto kern) {
-    kern<<<dim3((unsigned)grid), dim3(256), 0, s>>>(
+    kern<<<dim3((unsigned)p.grid), dim3(256), 0, s>>>(
         static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(k),
         static_cast<const uint16_t*>(v), static_cast<uint16_t*>(out), lse,
-        (int)nbk, (int)Hkv, (int)G, (int)T, (int)nqb, a, bb, c, lse_stride,
-        scale * 1.4426950408889634f);
+        (int)p.nbk, (int)Hkv, (int)p.G, (int)T, (int)p.nqb, strides3(qs),
+        strides3(ks), strides3(vs), lse_stride, scale * kLog2e);
   };
-  if (HW == 2)
+  if (p.HW == 2)
     launch(k_gqa_fwd_hd64<2>);
   else
     launch(k_gqa_fwd_hd64<4>);
