@@ -636,6 +636,18 @@ def bench_wgrad(out, rounds=7, iters=20, sweep=False):
                     arms[f"fused_v{v}_split{sp}"] = \
                         lambda v=v, sp=sp: fw.wgrad(dy, x, out=dw, variant=v,
                                                     split=sp)
+        # the 256 x 256 variant against what it would replace: the library
+        # call for the MLP shapes, variant 1 for the attention ones; for
+        # mlp.fc also kernel + column sums against mm + dy.sum(0)
+        v256 = max(fw.COLSUM_VARIANTS)
+        arms["fused_v1"] = lambda: fw.wgrad(dy, x, out=dw, variant=1)
+        arms["fused256"] = lambda: fw.wgrad(dy, x, out=dw, variant=v256)
+        if name == "mlp_fc":
+            db = torch.empty(N, dtype=torch.bfloat16, device="cuda")
+            arms["torch_mm_sum0"] = lambda: (torch.mm(dyt, x, out=dw),
+                                             torch.sum(dy, 0, out=db))
+            arms["fused256_db"] = lambda: fw.wgrad(dy, x, out=dw,
+                                                   variant=v256, db_out=db)
         for fn in arms.values():
             timed(fn)
         ms = {n: [] for n in arms}
@@ -650,6 +662,14 @@ def bench_wgrad(out, rounds=7, iters=20, sweep=False):
             rec[n] = dict(ms_median=round(med, 4),
                           ms_range=[round(xs[0], 4), round(xs[-1], 4)],
                           tflops=round(flop / med / 1e9, 1))
+        # the wiring rule: the median below the fastest round of the other
+        base = "torch_mm" if name.startswith("mlp") else "fused_v1"
+        rec["fused256_beats_" + base] = bool(
+            rec["fused256"]["ms_median"] < rec[base]["ms_range"][0])
+        if name == "mlp_fc":
+            rec["fused256_db_beats_torch_mm_sum0"] = bool(
+                rec["fused256_db"]["ms_median"]
+                < rec["torch_mm_sum0"]["ms_range"][0])
         out["wgrad_" + name] = rec
 
 

@@ -584,18 +584,22 @@ PYBIND11_MODULE(_core, m) {
         [](uintptr_t dy, uintptr_t x, uintptr_t dw, uintptr_t ws,
            int64_t ws_floats, int64_t M, int64_t N, int64_t K, int64_t ldy,
            int64_t ldx, int64_t ldw, int64_t split, int variant,
-           uintptr_t stream) {
+           uintptr_t stream, uintptr_t db, uintptr_t wsb,
+           int64_t wsb_floats) {
           hip_wgrad_bf16(reinterpret_cast<const void*>(dy),
                          reinterpret_cast<const void*>(x),
                          reinterpret_cast<void*>(dw),
                          reinterpret_cast<float*>(ws), ws_floats, M, N, K, ldy,
                          ldx, ldw, split, variant,
-                         reinterpret_cast<hipStream_t>(stream));
+                         reinterpret_cast<hipStream_t>(stream),
+                         reinterpret_cast<void*>(db),
+                         reinterpret_cast<float*>(wsb), wsb_floats);
         },
         py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("ws"),
         py::arg("ws_floats"), py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("ldy"), py::arg("ldx"), py::arg("ldw"), py::arg("split"),
-        py::arg("variant"), py::arg("stream"));
+        py::arg("variant"), py::arg("stream"), py::arg("db") = 0,
+        py::arg("wsb") = 0, py::arg("wsb_floats") = 0);
 
   // fused bf16 cross-entropy
   m.def("ce_fwd", [](uintptr_t logits, uintptr_t targets, uintptr_t loss,

@@ -430,11 +430,16 @@ void hip_gqa_attn_bwd_causal_hd64(
 // (split * N * K floats, 16-byte aligned, written before it is read) and a
 // second kernel sums them in split order: no atomics, the same bits on every
 // call.  Runs on stream `s`.  Throws on anything else.
+// `db` (optional, N bf16, 16-byte aligned; only the 256 x 256 variants take
+// it) receives the column sums of dY, taken in the same kernel from the rows
+// it stages; with split > 1 they go through `wsb` (split * N floats) and the
+// same second kernel.
 int hip_wgrad_num_variants();
 void hip_wgrad_tile(int variant, int* tile_n, int* tile_k);
 void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
                     int64_t ws_floats, int64_t M, int64_t N, int64_t K,
                     int64_t ldy, int64_t ldx, int64_t ldw, int64_t split,
-                    int variant, hipStream_t s);
+                    int variant, hipStream_t s, void* db = nullptr,
+                    float* wsb = nullptr, int64_t wsb_floats = 0);
 
 }  // namespace shamd

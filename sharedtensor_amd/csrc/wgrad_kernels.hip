@@ -238,16 +238,305 @@ __global__ __launch_bounds__(256 * NP * KP)
   }
 }
 
+// The 256 x 256 tile: the same split-K scheme, panels, swizzle, transposed
+// fragment reads and XCD remap as k_wgrad, with a larger register tile per
+// wave so that every fragment read from LDS feeds more MFMAs
+// (tests/test_wgrad256_resource_usage.py holds it to this plan).
+//   * a stage is 2 dY panels + 2 X panels, 64 KB; two stages, one barrier per
+//     step, one workgroup per CU.
+//   * 4 waves, one per SIMD; a wave owns 128 x 128 as 4 x 4 accumulators
+//     (256 registers, which the compiler keeps in AGPRs): 8 fragments per 16
+//     MFMAs against 4 per 4 in k_wgrad.
+//   * the fragments of the next 16-token step are read while the MFMAs of the
+//     current one issue.
+//   * CS: the workgroups of K-tile 0 also sum, in fp32, the dY values they
+//     stage (a thread always stages the same 8 feature columns of either dY
+//     panel), combine the NT / 16 threads of a column through LDS in a fixed
+//     order, and store the 256 column sums: as bf16 to db when split == 1,
+//     else as fp32 to wsb[split][N], which k_wgrad_reduce adds in split order.
+//     A split with no steps stores zeros.
+template <bool CS>
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(1, 1))) void k_wgrad256(
+    const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
+    uint16_t* __restrict__ dw, float* __restrict__ ws,
+    uint16_t* __restrict__ db, float* __restrict__ wsb, int steps, int N,
+    int K, int64_t ldy, int64_t ldx, int64_t ldw, int split, int tiles_k,
+    int tiles) {
+  constexpr int NW = 4, NT = 64 * NW;
+  constexpr int kStage = 4 * kPanelBytes;
+  constexpr int kC = 2 * 1024 / NT;  // 16-byte chunks per thread and operand
+  constexpr int BJ = 16 / NW;        // 32-column blocks of a wave's X range
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kStage];
+
+  // block id -> (split, tile): ids that share an XCD become consecutive
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int xcd = orig % kXcd, q8 = nwg / kXcd, r8 = nwg % kXcd;
+  const int wg =
+      (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) +
+      orig / kXcd;
+  const int sp = wg / tiles, tile = wg % tiles;
+  const int n0 = (tile / tiles_k) * 256;
+  const int k0 = (tile % tiles_k) * 256;
+  const bool colsum = CS && k0 == 0;  // the same for the whole workgroup
+
+  const int sq = steps / split, sr = steps % split;
+  const int s_begin = sp * sq + min(sp, sr);
+  const int s_count = sq + (sp < sr ? 1 : 0);
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int wn = wave / (NW / 2), wk = wave % (NW / 2);
+
+  // staging as in k_wgrad: chunk c = tid + i NT of an operand's two panels
+  const int srow = tid >> 4, sch = tid & 15;
+  uint4 sa0, sa1, sa2, sa3, sa4, sa5, sa6, sa7;
+  uint4 sb0, sb1, sb2, sb3, sb4, sb5, sb6, sb7;
+  float c0[8], c1[8];  // column sums of dY panel 0 and 1
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c0[e] = c1[e] = 0.f;
+  // a global address is a workgroup-uniform 64-bit part (scalar registers)
+  // plus a 32-bit byte offset per thread: 16 pointers per thread would not
+  // fit beside the accumulators (the launcher bounds the strides)
+  const char* const ga =
+      reinterpret_cast<const char*>(dy + (int64_t)s_begin * kStep * ldy + n0);
+  const char* const gb =
+      reinterpret_cast<const char*>(x + (int64_t)s_begin * kStep * ldx + k0);
+  const uint32_t va = 2u * (uint32_t)(srow * (int)ldy + 8 * sch);
+  const uint32_t vb = 2u * (uint32_t)(srow * (int)ldx + 8 * sch);
+#define SHAMD_WG_LOAD(reg, i, g, v, ld)                                      \
+  if constexpr ((i) < kC)                                                    \
+    reg = *reinterpret_cast<const uint4*>(                                   \
+        (g) + 2 * ((t + ((((i) * NT) & 1023) >> 4)) * (ld) +                 \
+                   (((i) * NT) >> 10) * kPanelCols) + (uint64_t)(v))
+#define SHAMD_WG_STORE(reg, i, p0)                                           \
+  if constexpr ((i) < kC)                                                    \
+    *reinterpret_cast<uint4*>(                                               \
+        base + ((p0) + (((i) * NT) >> 10)) * kPanelBytes +                   \
+        p_off(srow + ((((i) * NT) & 1023) >> 4), sch)) = reg
+#define SHAMD_WG_CSUM(reg, i)                                                \
+  if constexpr ((i) < kC) {                                                  \
+    float v[8];                                                              \
+    unpack8(reg, v);                                                         \
+    _Pragma("unroll") for (int e = 0; e < 8; ++e) {                          \
+      if constexpr ((((i) * NT) >> 10) != 0) c1[e] += v[e];                         \
+      else c0[e] += v[e];                                                    \
+    }                                                                        \
+  }
+  auto issue = [&](int step) {
+    const int64_t t = (int64_t)step * kStep;
+    SHAMD_WG_LOAD(sa0, 0, ga, va, ldy);
+    SHAMD_WG_LOAD(sa1, 1, ga, va, ldy);
+    SHAMD_WG_LOAD(sa2, 2, ga, va, ldy);
+    SHAMD_WG_LOAD(sa3, 3, ga, va, ldy);
+    SHAMD_WG_LOAD(sa4, 4, ga, va, ldy);
+    SHAMD_WG_LOAD(sa5, 5, ga, va, ldy);
+    SHAMD_WG_LOAD(sa6, 6, ga, va, ldy);
+    SHAMD_WG_LOAD(sa7, 7, ga, va, ldy);
+    SHAMD_WG_LOAD(sb0, 0, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb1, 1, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb2, 2, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb3, 3, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb4, 4, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb5, 5, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb6, 6, gb, vb, ldx);
+    SHAMD_WG_LOAD(sb7, 7, gb, vb, ldx);
+  };
+  auto commit = [&](int buf) {
+    unsigned char* const base = lds + buf * kStage;
+    SHAMD_WG_STORE(sa0, 0, 0);
+    SHAMD_WG_STORE(sa1, 1, 0);
+    SHAMD_WG_STORE(sa2, 2, 0);
+    SHAMD_WG_STORE(sa3, 3, 0);
+    SHAMD_WG_STORE(sa4, 4, 0);
+    SHAMD_WG_STORE(sa5, 5, 0);
+    SHAMD_WG_STORE(sa6, 6, 0);
+    SHAMD_WG_STORE(sa7, 7, 0);
+    SHAMD_WG_STORE(sb0, 0, 2);
+    SHAMD_WG_STORE(sb1, 1, 2);
+    SHAMD_WG_STORE(sb2, 2, 2);
+    SHAMD_WG_STORE(sb3, 3, 2);
+    SHAMD_WG_STORE(sb4, 4, 2);
+    SHAMD_WG_STORE(sb5, 5, 2);
+    SHAMD_WG_STORE(sb6, 6, 2);
+    SHAMD_WG_STORE(sb7, 7, 2);
+    if constexpr (CS) {
+      if (colsum) {
+        SHAMD_WG_CSUM(sa0, 0);
+        SHAMD_WG_CSUM(sa1, 1);
+        SHAMD_WG_CSUM(sa2, 2);
+        SHAMD_WG_CSUM(sa3, 3);
+        SHAMD_WG_CSUM(sa4, 4);
+        SHAMD_WG_CSUM(sa5, 5);
+        SHAMD_WG_CSUM(sa6, 6);
+        SHAMD_WG_CSUM(sa7, 7);
+      }
+    }
+  };
+#undef SHAMD_WG_LOAD
+#undef SHAMD_WG_STORE
+#undef SHAMD_WG_CSUM
+
+  f32x16 acc[4][BJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < BJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+  // fragment addressing as in k_wgrad; a wave's dY range is one whole panel
+  // and so is its X range
+  const int grp = lane >> 4, gi = lane & 15;
+  const int tr_q = gi >> 2, tr_p = gi & 3, hi = grp >> 1;
+  const int a_ch = 2 * (grp & 1) + (tr_p >> 1);
+  const int b_ch = a_ch;
+  const int a_panel = wn * kPanelBytes;
+  const int b_panel = (2 + wk) * kPanelBytes;
+
+  auto frag = [&](const unsigned char* panel, int ch, int ss) -> bf16x8 {
+    bf16x8 f;
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int row = 16 * ss + 8 * jj + 4 * hi + tr_q;
+      auto* a = reinterpret_cast<__attribute__((address_space(3))) s16x4*>(
+          (uintptr_t)(panel + p_off(row, ch) + 8 * (tr_p & 1)));
+      s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a);
+      bf16x4 tb = __builtin_bit_cast(bf16x4, tr);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[4 * jj + e] = tb[e];
+    }
+    return f;
+  };
+  auto compute = [&](int buf) {
+    const unsigned char* A = lds + buf * kStage + a_panel;
+    const unsigned char* B = lds + buf * kStage + b_panel;
+    // a[i] feeds the BJ MFMAs of row i and is read again for the next
+    // 16-token step right after them; b[j] is live through the whole step,
+    // so it has two copies
+    bf16x8 a[4], b[2][BJ];
+#pragma unroll
+    for (int j = 0; j < BJ; ++j) b[0][j] = frag(B, b_ch + 4 * j, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = frag(A, a_ch + 4 * i, 0);
+#pragma unroll
+    for (int ss = 0; ss < 4; ++ss) {
+      if (ss < 3) {
+#pragma unroll
+        for (int j = 0; j < BJ; ++j)
+          b[(ss + 1) & 1][j] = frag(B, b_ch + 4 * j, ss + 1);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < BJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              a[i], b[ss & 1][j], acc[i][j], 0, 0, 0);
+        if (ss < 3) a[i] = frag(A, a_ch + 4 * i, ss + 1);
+      }
+    }
+  };
+
+  // s_count is the same for the whole workgroup: every barrier below is
+  // reached by all of its waves or by none
+  if (s_count > 0) {
+    issue(0);
+    commit(0);
+    __syncthreads();
+    for (int t = 0; t < s_count; ++t) {
+      const bool more = t + 1 < s_count;
+      if (more) issue(t + 1);
+      compute(t & 1);
+      if (more) commit((t & 1) ^ 1);
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue, as in k_wgrad.  The scheduling barriers keep the row
+  // addresses of one 32 x 32 block at a time in registers: computed all at
+  // once, beside 256 accumulators, they spilled.
+  // A block stays in its accumulator registers until its turn.
+#define SHAMD_WG_PIN(v) asm volatile("" : "+a"(v))
+  const int row0 = n0 + wn * 128 + 4 * (lane >> 5);
+  const int col0 = k0 + wk * (32 * BJ) + (lane & 31);
+  if (split == 1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < BJ; ++j) {
+        uint16_t* o = dw + (int64_t)(row0 + 32 * i) * ldw + col0 + 32 * j;
+        SHAMD_WG_PIN(acc[i][j]);
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          o[((e & 3) + 8 * (e >> 2)) * ldw] = f32_to_bf16(acc[i][j][e]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  } else {
+    float* out = ws + (int64_t)sp * N * K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < BJ; ++j) {
+        float* o = out + (int64_t)(row0 + 32 * i) * K + col0 + 32 * j;
+        SHAMD_WG_PIN(acc[i][j]);
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          o[(int64_t)((e & 3) + 8 * (e >> 2)) * K] = acc[i][j][e];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  }
+#undef SHAMD_WG_PIN
+
+  if constexpr (CS) {
+    if (colsum) {
+      // the last barrier of the loop (or no loop at all) left the LDS free
+      float* red = reinterpret_cast<float*>(lds);  // [NT / 16][256]
+      float* mine = red + srow * 256 + 8 * sch;
+      *reinterpret_cast<float4*>(mine) = make_float4(c0[0], c0[1], c0[2], c0[3]);
+      *reinterpret_cast<float4*>(mine + 4) =
+          make_float4(c0[4], c0[5], c0[6], c0[7]);
+      *reinterpret_cast<float4*>(mine + 128) =
+          make_float4(c1[0], c1[1], c1[2], c1[3]);
+      *reinterpret_cast<float4*>(mine + 132) =
+          make_float4(c1[4], c1[5], c1[6], c1[7]);
+      __syncthreads();
+      if (tid < 256) {
+        float s = red[tid];
+        for (int r = 1; r < NT / 16; ++r) s += red[r * 256 + tid];
+        if (split == 1)
+          db[n0 + tid] = f32_to_bf16(s);
+        else
+          wsb[(int64_t)sp * N + n0 + tid] = s;
+      }
+    }
+  }
+}
+
 // dW = bf16(sum over splits, in index order, of ws[split][N][K]); a thread
-// owns 8 consecutive columns of one row (K is a multiple of 8)
+// owns 8 consecutive columns of one row (K is a multiple of 8).  With db, the
+// blocks after those of dW do the same for db = bf16(sum of wsb[split][N]).
 __global__ __launch_bounds__(256) void k_wgrad_reduce(
     const float* __restrict__ ws, uint16_t* __restrict__ dw, int64_t groups,
-    int K8, int64_t NK, int64_t ldw, int split) {
+    int K8, int64_t NK, int64_t ldw, int split,
+    const float* __restrict__ wsb, uint16_t* __restrict__ db, int N8) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= groups) return;
-  const int64_t row = g / K8;
-  const int col = (int)(g % K8) * 8;
-  const float* p = ws + row * (int64_t)(K8 * 8) + col;
+  const int64_t bias0 = (groups + 255) / 256 * 256;  // first thread of db
+  const float* p;
+  uint16_t* o;
+  int64_t stride;
+  if (g < groups) {
+    const int64_t row = g / K8;
+    const int col = (int)(g % K8) * 8;
+    p = ws + row * (int64_t)(K8 * 8) + col;
+    o = dw + row * ldw + col;
+    stride = NK;
+  } else if (g >= bias0 && g - bias0 < N8) {
+    p = wsb + (g - bias0) * 8;
+    o = db + (g - bias0) * 8;
+    stride = (int64_t)N8 * 8;
+  } else {
+    return;
+  }
   float v[8];
   {
     const float4 a = *reinterpret_cast<const float4*>(p);
@@ -256,18 +545,22 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(
     v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
   }
   for (int s = 1; s < split; ++s) {
-    const float4 a = *reinterpret_cast<const float4*>(p + s * NK);
-    const float4 b = *reinterpret_cast<const float4*>(p + s * NK + 4);
+    const float4 a = *reinterpret_cast<const float4*>(p + s * stride);
+    const float4 b = *reinterpret_cast<const float4*>(p + s * stride + 4);
     v[0] += a.x, v[1] += a.y, v[2] += a.z, v[3] += a.w;
     v[4] += b.x, v[5] += b.y, v[6] += b.z, v[7] += b.w;
   }
-  *reinterpret_cast<uint4*>(dw + row * ldw + col) = pack8(v);
+  *reinterpret_cast<uint4*>(o) = pack8(v);
 }
 
 struct Variant {
   int tile_n, tile_k;
+  bool colsum;  // can write db
 };
-constexpr Variant kVariants[] = {{128, 128}, {128, 128}, {256, 128}};
+constexpr Variant kVariants[] = {{128, 128, false},
+                                 {128, 128, false},
+                                 {256, 128, false},
+                                 {256, 256, true}};
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 }  // namespace
@@ -284,7 +577,8 @@ void hip_wgrad_tile(int variant, int* tile_n, int* tile_k) {
 void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
                     int64_t ws_floats, int64_t M, int64_t N, int64_t K,
                     int64_t ldy, int64_t ldx, int64_t ldw, int64_t split,
-                    int variant, hipStream_t s) {
+                    int variant, hipStream_t s, void* db, float* wsb,
+                    int64_t wsb_floats) {
   const char* op = "wgrad_bf16";
   auto fail = [&](const char* what) {
     throw std::runtime_error(std::string(op) + ": " + what);
@@ -297,6 +591,8 @@ void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
   if (ldy < N || ldx < K || ldw < K) fail("row stride shorter than the row");
   if (ldy % 8 || ldx % 8 || ldw % 8)
     fail("row strides must be multiples of 8 elements");
+  // k_wgrad256 keeps a thread's byte offset inside 64 rows in 32 bits
+  if (ldy > (1 << 24) || ldx > (1 << 24)) fail("row stride too large");
   check_align(dy, 16, op, "dy");
   check_align(x, 16, op, "x");
   check_align(dw, 16, op, "dw");
@@ -311,9 +607,19 @@ void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
       fail("workspace smaller than split * N * K floats");
     check_align(ws, 16, op, "ws");
   }
+  if (db != nullptr) {
+    if (!kVariants[variant].colsum) fail("this variant takes no db");
+    check_align(db, 16, op, "db");
+    if (split > 1) {
+      if (wsb == nullptr || wsb_floats < split * N)
+        fail("db workspace smaller than split * N floats");
+      check_align(wsb, 16, op, "wsb");
+    }
+  }
   auto* dyp = static_cast<const uint16_t*>(dy);
   auto* xp = static_cast<const uint16_t*>(x);
   auto* dwp = static_cast<uint16_t*>(dw);
+  auto* dbp = static_cast<uint16_t*>(db);
   const dim3 grid((unsigned)(tiles * split));
   const int tiles_k = (int)(K / tk);
 #define SHAMD_WGRAD_LAUNCH(NP, KP, NBUF)                                     \
@@ -323,15 +629,24 @@ void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
   switch (variant) {
     case 0: SHAMD_WGRAD_LAUNCH(1, 1, 2); break;
     case 1: SHAMD_WGRAD_LAUNCH(1, 1, 1); break;
-    default: SHAMD_WGRAD_LAUNCH(2, 1, 2); break;
+    case 2: SHAMD_WGRAD_LAUNCH(2, 1, 2); break;
+    default:
+      dispatch_bool(db != nullptr, [&](auto cs) {
+        k_wgrad256<decltype(cs)::value><<<grid, dim3(256), 0, s>>>(
+            dyp, xp, dwp, ws, dbp, wsb, (int)steps, (int)N, (int)K, ldy, ldx,
+            ldw, (int)split, tiles_k, (int)tiles);
+      });
+      break;
   }
 #undef SHAMD_WGRAD_LAUNCH
   HIP_CHECK(hipGetLastError());
   if (split > 1) {
     const int64_t groups = N * K / 8;
-    k_wgrad_reduce<<<dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
-                     s>>>(ws, dwp, groups, (int)(K / 8), N * K, ldw,
-                          (int)split);
+    const int64_t blocks =
+        (groups + 255) / 256 + (db != nullptr ? (N / 8 + 255) / 256 : 0);
+    k_wgrad_reduce<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(
+        ws, dwp, groups, (int)(K / 8), N * K, ldw, (int)split, wsb, dbp,
+        db != nullptr ? (int)(N / 8) : 0);
     HIP_CHECK(hipGetLastError());
   }
 }

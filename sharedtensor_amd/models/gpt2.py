@@ -95,12 +95,14 @@ FUSE_QKV_ATTN_BWD = True
 
 # Take the weight gradient of the four layer Linears (attn.qkv, attn.proj,
 # mlp.fc, mlp.proj) from our split-K kernel (ops/fused_wgrad.py) instead of
-# the library's NT GEMM; forward, dX and the bias gradients stay where they
-# are.  Only the weight shapes in fused_wgrad.TUNED, the ones that won their
-# measurement, take it: attn.proj 0.099 ms against 0.173 ms for the tuned
-# library GEMM and attn.qkv 0.303 against 0.336.  mlp.fc (0.410 against
-# 0.394) and mlp.proj (0.414 against 0.404) lost and keep aten, as does
-# lm_head (large output, tied weight).  Numbers in profiles/r09/.
+# the library's NT GEMM; forward and dX stay where they are.  Only the weight
+# shapes in fused_wgrad.TUNED, the ones that won their measurement, take it:
+# attn.proj 0.099 ms against 0.173 ms for the tuned library GEMM with the
+# 128 x 128 tile (profiles/r09/); with the 256 x 256 tile (profiles/r16/)
+# attn.qkv 0.289 ms against 0.302, mlp.proj 0.367 against 0.391 for the
+# library, and mlp.fc, whose bias gradient the same kernel takes from the dY
+# rows it stages, 0.361 against 0.462 for the library GEMM plus dy.sum(0).
+# lm_head (large output, tied weight) keeps aten.
 # SHTENS_FUSED_WGRAD = 0 or 1 overrides the flag for an A/B run.
 FUSE_WGRAD = True
 

@@ -12,6 +12,11 @@ contiguous ranges of 64-token steps; the partial tiles go through an fp32
 workspace ``[split][N][K]`` and a second kernel adds them in split order.  No
 atomics: two calls on the same inputs give the same bits.
 
+The 256 x 256 variant can also write the bias gradient (the column sums of
+``dY``): the workgroups of its first column of tiles sum the ``dY`` rows they
+stage anyway, through a second workspace ``[split][N]`` and the same second
+kernel.
+
 ``can_use`` says whether the kernel takes the operands; ``linear_wgrad``
 computes the same thing in plain torch for everything else (CPU included).
 A call that passes ``can_use`` and then fails is an error, never a silent
@@ -33,12 +38,19 @@ NUM_CU = 256       # MI355X
 #   1: 128 x 128, 4 waves, one LDS stage (32 KB), 3 fit; sizing the split
 #      for 2 measured faster than for 3 (profiles/r09/)
 #   2: 256 x 128, 8 waves, two LDS stages (96 KB), 1 fits
-VARIANTS = {0: (128, 128, 2), 1: (128, 128, 2), 2: (256, 128, 1)}
+#   3: 256 x 256, 4 waves of 128 x 128, two LDS stages (128 KB), 1 fits
+VARIANTS = {0: (128, 128, 2), 1: (128, 128, 2), 2: (256, 128, 1),
+            3: (256, 256, 1)}
 DEFAULT_VARIANT = 1
+# the variants that can write the column sums of dY (``db_out``)
+COLSUM_VARIANTS = frozenset({3})
 
-# (N, K) of a weight -> variant, for the shapes whose microbenchmark beat the
-# tuned library GEMM (profiles/r09/); models/gpt2.py routes only these
-TUNED: dict = {(768, 768): 1, (2304, 768): 1}
+# (N, K) of a weight -> variant, for the shapes whose microbenchmark beat what
+# they had before: the tuned library GEMM (profiles/r09/), or, for the
+# 256 x 256 variant (profiles/r16/), the library on the two MLP shapes and
+# variant 1 on attn.qkv.  attn.proj (9 tiles of 256 x 256, split 28) measured
+# slower with it and keeps variant 1.  models/gpt2.py routes only these
+TUNED: dict = {(768, 768): 1, (2304, 768): 3, (3072, 768): 3, (768, 3072): 3}
 
 
 def split_ranges(steps: int, split: int) -> List[Tuple[int, int]]:
@@ -99,10 +111,14 @@ def _workspace_for(device, n: int, stream: int) -> torch.Tensor:
 
 def wgrad(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None,
           split: Optional[int] = None, variant: Optional[int] = None,
-          ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+          ws: Optional[torch.Tensor] = None,
+          db_out: Optional[torch.Tensor] = None,
+          wsb: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Launch the kernels on the current stream; returns dW (N, K) bf16.
     ``out`` (rows may be strided), ``split`` and ``ws`` may be passed in
-    (tests put guard regions around ``out`` and ``ws``)."""
+    (tests put guard regions around ``out`` and ``ws``).  ``db_out`` (N,)
+    bf16, for a variant in ``COLSUM_VARIANTS``, receives ``dy.sum(0)``; its
+    split partials go through ``wsb`` (split * N floats)."""
     from .. import _core
     if variant is None:
         variant = TUNED.get((dy.shape[1], x.shape[1]), DEFAULT_VARIANT)
@@ -119,10 +135,29 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None,
                          "column stride and an aligned row stride")
     if split is None:
         split = choose_split((N // tn) * (K // tk), M // STEP, per_cu)
+    if db_out is not None:
+        if variant not in COLSUM_VARIANTS:
+            raise ValueError("fused_wgrad: this variant writes no db_out")
+        if (db_out.shape != (N,) or db_out.dtype != torch.bfloat16
+                or db_out.device != dy.device or not db_out.is_contiguous()
+                or db_out.data_ptr() % 16):
+            raise ValueError("fused_wgrad: db_out must be (N,) contiguous "
+                             "bf16, 16-byte aligned")
     s = torch.cuda.current_stream(dy.device).cuda_stream
     need = split * N * K if split > 1 else 0
+    need_b = split * N if split > 1 and db_out is not None else 0
     if need and ws is None:
-        ws = _workspace_for(dy.device, need, s)
+        # one buffer per stream covers both workspaces
+        both = _workspace_for(dy.device, need + need_b, s)
+        ws = both[:need]
+        if need_b and wsb is None:
+            wsb = both[need:need + need_b]
+    if need_b and wsb is None:
+        wsb = torch.empty(need_b, dtype=torch.float32, device=dy.device)
+    if need_b and (wsb.dtype != torch.float32 or not wsb.is_contiguous()
+                   or wsb.numel() < need_b or wsb.device != dy.device):
+        raise ValueError("fused_wgrad: wsb must be contiguous fp32 with at "
+                         "least split * N elements")
     if need and (ws.dtype != torch.float32 or not ws.is_contiguous()
                  or ws.numel() < need or ws.device != dy.device):
         raise ValueError("fused_wgrad: ws must be contiguous fp32 with at "
@@ -130,7 +165,10 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None,
     _core.wgrad_bf16(dy.data_ptr(), x.data_ptr(), out.data_ptr(),
                      ws.data_ptr() if need else 0, ws.numel() if need else 0,
                      M, N, K, dy.stride(0), x.stride(0), out.stride(0),
-                     split, variant, s)
+                     split, variant, s,
+                     db_out.data_ptr() if db_out is not None else 0,
+                     wsb.data_ptr() if need_b else 0,
+                     wsb.numel() if need_b else 0)
     return out
 
 
@@ -157,13 +195,18 @@ class _LinearWgrad(torch.autograd.Function):
         with torch.autocast(device_type=dy.device.type, enabled=False):
             if ctx.needs_input_grad[0]:
                 dx = dy2.to(weight.dtype).mm(weight).to(x.dtype).view(x.shape)
+            want_db = ctx.has_bias and ctx.needs_input_grad[2]
             if ctx.needs_input_grad[1]:
                 variant = TUNED.get(tuple(weight.shape), DEFAULT_VARIANT)
                 if weight.dtype == torch.bfloat16 and can_use(dy2, x2, variant):
-                    dw = wgrad(dy2, x2, variant=variant)
+                    if want_db and variant in COLSUM_VARIANTS:
+                        # the kernel stages these dY rows anyway
+                        db = torch.empty(dy2.shape[1], dtype=dy2.dtype,
+                                         device=dy2.device)
+                    dw = wgrad(dy2, x2, variant=variant, db_out=db)
                 else:
                     dw = dy2.t().to(weight.dtype).mm(x2.to(weight.dtype))
-            if ctx.has_bias and ctx.needs_input_grad[2]:
+            if want_db and db is None:
                 db = dy2.sum(0)
         return dx, dw, db
 
@@ -172,7 +215,8 @@ def linear_wgrad(x: torch.Tensor, weight: torch.Tensor,
                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``F.linear(x, weight, bias)``; in the backward ``weight.grad`` comes
     from the split-K kernel where ``can_use`` holds and from torch's matmul
-    everywhere else."""
+    everywhere else; ``bias.grad`` comes from the same kernel where the
+    shape's variant can write it, and from ``dy.sum(0)`` otherwise."""
     return _LinearWgrad.apply(x, weight, bias)
 
 
