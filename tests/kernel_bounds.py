@@ -1,5 +1,6 @@
 """fp64 references and derived error bounds for the bf16 model kernels
-(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU), for the fused
+(block-per-row LayerNorm / RMSNorm, colsum, GELU, SwiGLU, and the
+wave-per-row add+LayerNorm / add+RMSNorm kernels), for the fused
 fp32 optimizers (AdamW, SGD momentum) and, at the end of the file, for the
 fused cross-entropy kernels.
 
@@ -21,7 +22,9 @@ dbeta, colsum) are held to the slack alone.
 Reduction depth.  A row statistic is summed by 256 threads: each adds its
 ceil(C/512) bf16 pairs serially (2 adds per pair), then 6 shuffle levels and
 3 LDS adds, then one divide: n_red(C) = 2*ceil(C/512) + 10.  Column sums
-over R rows are bounded for any order (serial, atomics): n = R + 3.
+over R rows are bounded for any order (serial, atomics): n = R + 3.  The
+wave-per-row kernels sum a row differently; their depths are wave_depths(),
+which the slack functions take as `depth`.
 
 Transcendentals.  tanhf is given 4 fp32 ulps of its value.  The fast exp is
 exp2(x * log2(e)) with the product rounded to fp32, a relative error of
@@ -52,6 +55,17 @@ EPS32 = float(np.float32(EPS))  # what the kernel receives
 
 def n_red(C: int) -> int:
     return 2 * math.ceil(C / 512) + 10
+
+
+def _depths(depth, C):
+    """(mean, var, row) reduction depths: None is the block-per-row n_red(C)
+    for all three, an int that number for all three, a dict as wave_depths
+    returns it ("mean" is absent for RMSNorm)."""
+    if depth is None:
+        depth = n_red(C)
+    if isinstance(depth, dict):
+        return depth.get("mean", 0), depth["var"], depth["row"]
+    return depth, depth, depth
 
 
 # ------------------------------------------------------------------ bound
@@ -139,11 +153,12 @@ def rms_formula(x, w, dy=None, dtype=torch.float64, eps=EPS32):
     return out
 
 
-def rms_slack(x, w, dy=None, eps=EPS32):
-    """Running-error bounds for rms_formula evaluated in fp32."""
+def rms_slack(x, w, dy=None, eps=EPS32, depth=None):
+    """Running-error bounds for rms_formula evaluated in fp32.  `depth`: see
+    _depths; the sum of squares is n deep, the backward row sum nr."""
     x, w = x.double(), w.double()
     R, C = x.shape
-    n = n_red(C)
+    _, n, nr = _depths(depth, C)
     rs = torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
     # sum of squares: all terms positive, relative error (n + 2)u; the
     # inverse square root halves it; 4u for add, divide and rsqrt
@@ -155,7 +170,7 @@ def rms_slack(x, w, dy=None, eps=EPS32):
         g = dy * w
         gx = g * x
         t = rs * rs * gx.mean(-1, keepdim=True)
-        t_err = (rs * rs * (n + 3) * U * gx.abs().mean(-1, keepdim=True)
+        t_err = (rs * rs * (nr + 3) * U * gx.abs().mean(-1, keepdim=True)
                  + t.abs() * (2 * d_rs + 3 * U))
         mag = g.abs() + (x * t).abs()
         dx = rs * (g - x * t)
@@ -186,21 +201,22 @@ def ln_formula(x, w, b=None, dy=None, dtype=torch.float64, eps=EPS32):
     return out
 
 
-def ln_slack(x, w, b=None, dy=None, eps=EPS32):
+def ln_slack(x, w, b=None, dy=None, eps=EPS32, depth=None):
     """Running-error bounds for ln_formula evaluated in fp32 (two-pass
-    variance)."""
+    variance).  `depth`: see _depths; the mean is nm deep, the variance nv,
+    the two backward row sums nr."""
     x, w = x.double(), w.double()
     R, C = x.shape
-    n = n_red(C)
+    nm, nv, nr = _depths(depth, C)
     m = x.mean(-1, keepdim=True)
     d = x - m
     var = (d * d).mean(-1, keepdim=True)
     rs = torch.rsqrt(var + eps)
     h = d * rs
-    m_err = n * U * x.abs().mean(-1, keepdim=True)
+    m_err = nm * U * x.abs().mean(-1, keepdim=True)
     # (x - m)^2 with m off by m_err, then a sum of positive terms
     var_err = (2 * m_err * d.abs().mean(-1, keepdim=True) + m_err * m_err
-               + (n + 3) * U * var)
+               + (nv + 3) * U * var)
     rs_err = 0.5 * rs ** 3 * var_err + 3 * U * rs
     h_err = rs * (m_err + U * d.abs()) + d.abs() * rs_err + U * h.abs()
     babs = b.double().abs() if b is not None else 0.0
@@ -211,8 +227,8 @@ def ln_slack(x, w, b=None, dy=None, eps=EPS32):
         g = dy * w
         t1 = g.mean(-1, keepdim=True)
         t2 = (g * h).mean(-1, keepdim=True)
-        t1_err = (n + 1) * U * g.abs().mean(-1, keepdim=True)
-        t2_err = ((n + 3) * U * (g * h).abs().mean(-1, keepdim=True)
+        t1_err = (nr + 1) * U * g.abs().mean(-1, keepdim=True)
+        t2_err = ((nr + 3) * U * (g * h).abs().mean(-1, keepdim=True)
                   + (g.abs() * h_err).mean(-1, keepdim=True))
         inner = g - t1 - h * t2
         inner_err = (t1_err + h.abs() * t2_err + t2.abs() * h_err
@@ -408,17 +424,18 @@ def swiglu_slack(x1, x3, dy=None):
 
 # ----------------------------------------------- wrapper-level norm checks
 
-def check_ln_wrapper(fused_layer_norm, x, w, b, dy, family, eps=EPS):
+def check_ln_wrapper(fused_layer_norm, x, w, b, dy, family, eps=EPS,
+                     depth=None):
     """fused_layer_norm forward + backward on 2-D bf16 inputs against the
     fp64 reference: y, dx, and the bf16 weight gradients, each 1 ulp +
-    slack.  Returns the kernel's outputs."""
+    slack (`depth` as ln_slack takes it).  Returns the kernel's outputs."""
     xf = x.clone().requires_grad_(True)
     wf = w.clone().requires_grad_(True)
     bf = b.clone().requires_grad_(True) if b is not None else None
     y = fused_layer_norm(xf, wf, bf, eps)
     y.backward(dy)
     ref = ln_formula(x, w, b, dy)
-    slack = ln_slack(x, w, b, dy)
+    slack = ln_slack(x, w, b, dy, depth=depth)
     got = {"y": y.detach(), "dx": xf.grad, "dgamma": wf.grad}
     if b is not None:
         got["dbeta"] = bf.grad
@@ -428,18 +445,267 @@ def check_ln_wrapper(fused_layer_norm, x, w, b, dy, family, eps=EPS):
     return got
 
 
-def check_rms_wrapper(fused_rms_norm, x, w, dy, family, eps=EPS):
+def check_rms_wrapper(fused_rms_norm, x, w, dy, family, eps=EPS,
+                      depth=None):
     xf = x.clone().requires_grad_(True)
     wf = w.clone().requires_grad_(True)
     y = fused_rms_norm(xf, wf, eps)
     y.backward(dy)
     ref = rms_formula(x, w, dy)
-    slack = rms_slack(x, w, dy)
+    slack = rms_slack(x, w, dy, depth=depth)
     got = {"y": y.detach(), "dx": xf.grad, "dgamma": wf.grad}
     for k, v in got.items():
         assert v.dtype == torch.bfloat16 and v.shape == ref[k].shape, k
         assert_bf16(v, ref[k], slack[k], "rms", k, family)
     return got
+
+
+# ------------------------------ wave-per-row add+LayerNorm and add+RMSNorm
+#
+# csrc/add_ln_kernels.hip (C = 256 * NV, a lane owns 4 elements per chunk)
+# and csrc/add_rms_kernels.hip (C = 512 * NV, 8 elements per chunk): one
+# 64-lane wave per row, NV chunks per lane, the row sums through wave_sum, a
+# 6-level butterfly, then `* (1.f / C)`: the constant is rounded and so is
+# the product, 2 roundings (C = 768 is no power of two).  Read off the code:
+#
+#   LN mean      s += (v0 + v1) + (v2 + v3) per chunk: 2 pair adds, then the
+#                NV chained adds of s:                  NV + 2, + 6 + 2
+#   LN variance  q += d * d, element by element:       4 NV,    + 6 + 2
+#   LN backward  s1 += g and s2 += g * h likewise:      4 NV,    + 6 + 2
+#   RMS sum of squares q += v * v:                     8 NV,    + 6 + 2
+#   RMS backward s += d * w * h:                       8 NV,    + 6 + 2
+#
+# At C = 1024 the LayerNorm variance is 24 deep against n_red = 14, at
+# C = 4096 the RMSNorm sum 72 against 26.
+#
+# Outputs the block-per-row kernels do not have.  dx_total = dx + d_x_new
+# is one more fp32 add before the single bf16 rounding: the dx slack plus
+# U * |dx + d_x_new|.  ddbias = sum_rows(dx_total) is summed from the fp32
+# values before that rounding: the column sum of the per-element slack plus
+# (R + 3) * U * sum|dx_total|.  Each column of dgamma, dbeta and ddbias is
+# summed over the R rows in a fixed tree (a lane's rows in turn, the block's
+# four waves in order, the partial rows in the reducer's tree); summands
+# that are exactly zero add no error, every one of the R terms passes at most
+# R - 1 adds in any tree, and the any-order count R + 3 of the block-per-row
+# bound covers it.  The three leave the kernels as bf16: 1 ulp + that slack.
+
+def wave_depths(op, C):
+    """Reduction depths of the wave-per-row kernels, as _depths takes them."""
+    if op == "ln":
+        nv = C // 256
+        return {"mean": nv + 2 + 6 + 2, "var": 4 * nv + 6 + 2,
+                "row": 4 * nv + 6 + 2}
+    nv = C // 512
+    return {"var": 8 * nv + 6 + 2, "row": 8 * nv + 6 + 2}
+
+
+def add_norm_formula(op, x, w, b, dy, dres, dtype=torch.float64):
+    """ln_formula / rms_formula on the bf16 x_new, plus dx_total and (LN)
+    ddbias.  `dres` is d_x_new or None."""
+    out = (ln_formula(x, w, b, dy, dtype) if op == "ln"
+           else rms_formula(x, w, dy, dtype))
+    out["dx_total"] = out["dx"] if dres is None else out["dx"] + dres.to(dtype)
+    if op == "ln":
+        out["ddbias"] = out["dx_total"].sum(0)
+    return out
+
+
+def add_norm_slack(op, x, w, b, dy, dres):
+    R, C = x.shape
+    depth = wave_depths(op, C)
+    out = (ln_slack(x, w, b, dy, depth=depth) if op == "ln"
+           else rms_slack(x, w, dy, depth=depth))
+    tot = add_norm_formula(op, x, w, b, dy, dres)["dx_total"]
+    out["dx_total"] = out["dx"] + (U * tot.abs() if dres is not None else 0.0)
+    if op == "ln":
+        out["ddbias"] = out["dx_total"].sum(0) + (R + 3) * U * tot.abs().sum(0)
+    return out
+
+
+ADD_NORM_FAMILIES = NORM_FAMILIES + ["dres_cancel"]
+ADD_NORM_BF16 = ("y", "dx_total", "dgamma", "dbeta", "ddbias")
+ADD_NORM_F32 = ("mean", "rstd")
+
+
+def add_norm_inputs(op, family, R, C, seed=0):
+    """The x_new the family asks for, w, b, dy (norm_inputs; dres_cancel uses
+    those of randn2), and a delta / delta_bias to reach x_new with: multiples
+    of 0.5 in [-4, 4], so that bf16(x_new - delta) + delta is x_new again
+    wherever the family's point is an exact value (constant, shifted).  bf16,
+    on the CPU."""
+    base = "randn2" if family == "dres_cancel" else family
+    x, w, b, dy = norm_inputs(base, R, C, seed)
+    g = torch.Generator().manual_seed(1000 * seed + 7 * R + C + 1)
+    delta = (torch.randint(-8, 9, (R, C), generator=g) * 0.5).bfloat16()
+    dbias = (torch.randint(-8, 9, (C,), generator=g) * 0.5).bfloat16()
+    return {"x": x, "w": w, "b": b, "dy": dy, "delta": delta, "dbias": dbias}
+
+
+def add_norm_dres(op, family, x_new, w, dy, seed=0):
+    """d_x_new for the x_new the forward produced.  dres_cancel: minus the
+    bf16 rounding of the reference dx, so that dx_total is the rounding
+    residue of dx; a kernel that rounds dx to bf16 before the add is off by
+    up to half a bf16 ulp of dx there.  Otherwise Gaussian."""
+    if family == "dres_cancel":
+        f = (ln_formula(x_new, w, None, dy) if op == "ln"
+             else rms_formula(x_new, w, dy))
+        return -(f["dx"].to(torch.bfloat16))
+    R, C = x_new.shape
+    g = torch.Generator().manual_seed(1000 * seed + 7 * R + C + 2)
+    return torch.randn(R, C, generator=g).to(torch.bfloat16).to(x_new.device)
+
+
+def check_add_norm(op, got, x_new, w, b, dy, dres, family, tag=None):
+    """Every output in `got` against the fp64 reference on x_new: the bf16
+    ones 1 ulp + slack, mean / rstd the fp32 slack.  Returns (ref, slack)."""
+    name = tag or "add_" + op
+    ref = add_norm_formula(op, x_new, w, b, dy, dres)
+    slack = add_norm_slack(op, x_new, w, b, dy, dres)
+    for k, v in got.items():
+        assert v.shape == ref[k].shape, (k, v.shape, ref[k].shape)
+        if k in ADD_NORM_F32:
+            assert v.dtype == torch.float32, k
+            assert_f32(v, ref[k], slack[k], name, k, family)
+        else:
+            assert v.dtype == torch.bfloat16, k
+            assert_bf16(v, ref[k], slack[k], name, k, family)
+    return ref, slack
+
+
+def emu_wave_sum(v: np.ndarray) -> np.ndarray:
+    """wave_sum in fp32 over the last axis (64 lanes): the xor butterfly,
+    which leaves the same total in every lane."""
+    a = v.astype(np.float32)
+    idx = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        a = a + a[..., idx ^ o]
+    return a[..., 0]
+
+
+def emu_colsum(terms, reducer, gmax=1024, row_weight=None):
+    """Column sums of the fp32 (R, C) `terms` in the backward kernels' order:
+    row r belongs to wave r % 4 of block (r // 4) % G, a lane adds its rows
+    in turn, the block adds its four waves in order, and the G partial rows
+    go through k_colsum_reduce ("colsum": 64 row groups, then 4 at a time,
+    then 16) or k_add_rms_reduce ("rms": 16 row groups, then 16).  G is
+    min(ceil(R / 4), gmax).  `row_weight` scales rows (a dropped or doubled
+    row, for the mutants)."""
+    f = np.float32
+    R, C = terms.shape
+    if row_weight is not None:
+        terms = terms * np.asarray(row_weight, f)[:, None]
+    G = min((R + 3) // 4, gmax)
+    it = -(-R // (4 * G))
+    T = np.zeros((it * G * 4, C), f)
+    T[:R] = terms
+    T = T.reshape(it, G, 4, C)
+    acc = np.zeros((G, 4, C), f)
+    for i in range(it):
+        acc = acc + T[i]
+    part = ((acc[:, 0] + acc[:, 1]) + acc[:, 2]) + acc[:, 3]
+    ng = 64 if reducer == "colsum" else 16
+    nr = -(-G // ng)
+    P = np.zeros((nr * ng, C), f)
+    P[:G] = part
+    P = P.reshape(nr, ng, C)
+    a = np.zeros((ng, C), f)
+    for i in range(nr):
+        a = a + P[i]
+    if reducer == "colsum":
+        a4 = a.reshape(16, 4, C)
+        a = np.zeros((16, C), f)
+        for i in range(4):
+            a = a + a4[:, i]
+    u = np.zeros(C, f)
+    for i in range(16):
+        u = u + a[i]
+    return u
+
+
+def emu_add_norm(op, x, w, b, dy, dres, eps=EPS32, gmax=1024, inv_c=None,
+                 one_pass=False, round_first=False, dgamma_dyw=False,
+                 row_weight=None):
+    """k_add_ln_fwd + k_add_ln_bwd (op "ln") or k_add_rms_fwd + k_add_rms_bwd
+    ("rms") on the bf16 x_new `x` in fp32, in the kernels' lane layout and
+    summation order (no fused multiply-add; the bounds hold with or without).
+    Returns what the kernels store, bf16 and fp32 as they do.
+
+    Mutants: `inv_c` another instantiation's 1 / C; `one_pass` the
+    E[x^2] - m^2 variance; `eps` = 0; `round_first` dx rounded to bf16 before
+    d_x_new is added; `dgamma_dyw` dgamma accumulated from dy * w; and
+    `row_weight` (emu_colsum)."""
+    f = np.float32
+    R, C = x.shape
+    E = 4 if op == "ln" else 8
+    NV = C // (64 * E)
+
+    def lay(t):
+        return t.float().numpy().astype(f).reshape(-1, NV, 64, E)
+
+    def rows(a):                        # a per-row scalar against (R, NV, 64, E)
+        return a[:, None, None, None]
+
+    def bf16(a):
+        return torch.from_numpy(a.reshape(R, C)).to(torch.bfloat16)
+
+    v, ww, d = lay(x), lay(w), lay(dy)
+    ic = f(1) / f(C) if inv_c is None else f(inv_c)
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if op == "ln":
+            s = np.zeros((R, 64), f)
+            for k in range(NV):
+                s = s + ((v[:, k, :, 0] + v[:, k, :, 1])
+                         + (v[:, k, :, 2] + v[:, k, :, 3]))
+            m = emu_wave_sum(s) * ic
+            out["mean"] = torch.from_numpy(m)
+        else:
+            m = np.zeros(R, f)
+        cen = v - rows(m) if op == "ln" else v
+        q = np.zeros((R, 64), f)
+        for k in range(NV):
+            for j in range(E):
+                t = v[:, k, :, j] if one_pass else cen[:, k, :, j]
+                q = q + t * t
+        var = emu_wave_sum(q) * ic
+        if one_pass:
+            var = np.maximum(var - m * m, f(0))
+        rs = (f(1) / np.sqrt(var + f(eps))).astype(f)
+        out["rstd"] = torch.from_numpy(rs)
+        h = cen * rows(rs)
+        y = h * ww
+        if b is not None:
+            y = y + lay(b)
+        out["y"] = bf16(y)
+
+        g = d * ww
+        s1 = np.zeros((R, 64), f)
+        s2 = np.zeros((R, 64), f)
+        for k in range(NV):
+            for j in range(E):
+                s1 = s1 + g[:, k, :, j]
+                s2 = s2 + g[:, k, :, j] * h[:, k, :, j]
+        t2 = emu_wave_sum(s2) * ic
+        if op == "ln":
+            t1 = emu_wave_sum(s1) * ic
+            o = ((g - rows(t1)) - h * rows(t2)) * rows(rs)
+        else:
+            o = (g - h * rows(t2)) * rows(rs)
+        if round_first:
+            o = bf16(o).float().numpy().reshape(o.shape)
+        if dres is not None:
+            o = o + lay(dres)
+        out["dx_total"] = bf16(o)
+        red = "colsum" if op == "ln" else "rms"
+
+        def col(a):
+            return torch.from_numpy(emu_colsum(
+                a.reshape(R, C), red, gmax, row_weight)).to(torch.bfloat16)
+        out["dgamma"] = col((g if dgamma_dyw else d) * h)
+        if op == "ln":
+            out["dbeta"] = col(d)
+            out["ddbias"] = col(o)
+    return out
 
 
 # ------------------------------------------------------- fused optimizers

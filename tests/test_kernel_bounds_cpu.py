@@ -2,7 +2,9 @@
 in fp32 and rounded to bf16 must meet the bound the GPU tests hold the
 kernels to, with no exceptions, for every input family; and the bound must
 still reject the errors it exists to find (one-pass LayerNorm variance on a
-shifted row, a 1 % error in a constant)."""
+shifted row, a 1 % error in a constant).  For the wave-per-row add+LayerNorm
+and add+RMSNorm kernels the fp32 evaluation is one in the kernels' own lane
+layout and summation order, and the mutants are listed with their tests."""
 import numpy as np
 import pytest
 import torch
@@ -112,6 +114,176 @@ def test_bound_rejects_small_norm_errors():
     with pytest.raises(AssertionError):
         kb.assert_f32(short, ref["dgamma"], slack["dgamma"], "rms", "dgamma",
                       "dropped-row")
+
+
+# --------------------------- wave-per-row add+LayerNorm and add+RMSNorm
+
+# the narrowest and the widest instantiation of each kernel, and the widths
+# of GPT-2-small and Llama-1B
+WAVE_WIDTHS = {"ln": [256, 768, 1024], "rms": [512, 2048, 4096]}
+WAVE_CASES = [(op, C) for op in ("ln", "rms") for C in WAVE_WIDTHS[op]]
+
+
+def _wave_case(op, family, R, C, sentinel=()):
+    """Inputs of one backward call as the GPU test builds them: x_new is the
+    family's x itself (the delta = None call)."""
+    t = kb.add_norm_inputs(op, family, R, C)
+    x, w, dy = t["x"], t["w"], t["dy"]
+    b = t["b"] if op == "ln" else None
+    dres = kb.add_norm_dres(op, family, x, w, dy)
+    for r in sentinel:
+        dy, dres = dy.clone(), dres.clone()
+        dy[r] *= 64
+        dres[r] *= 64
+    return x, w, b, dy, dres
+
+
+def _wave_judge(op, got, args, family):
+    try:
+        kb.check_add_norm(op, got, *args, family, tag=f"add_{op}-emu")
+    except AssertionError:
+        return False
+    return True
+
+
+def test_wave_depths_are_the_ones_read_off_the_code():
+    assert kb.wave_depths("ln", 768) == {"mean": 3 + 2 + 6 + 2,
+                                         "var": 12 + 6 + 2, "row": 12 + 6 + 2}
+    assert kb.wave_depths("ln", 1024)["var"] == 24 > kb.n_red(1024) == 14
+    assert kb.wave_depths("rms", 4096)["var"] == 72 > kb.n_red(4096) == 26
+    assert kb.wave_depths("rms", 512) == {"var": 16, "row": 16}
+
+
+def test_default_depth_leaves_the_block_per_row_slack_as_it_was():
+    x, w, b, dy = kb.norm_inputs("randn2", 5, 1280)
+    n = kb.n_red(1280)
+    a, c = kb.ln_slack(x, w, b, dy), kb.ln_slack(x, w, b, dy, depth=n)
+    assert a.keys() == c.keys() and all(torch.equal(a[k], c[k]) for k in a)
+    a, c = kb.rms_slack(x, w, dy), kb.rms_slack(x, w, dy, depth=n)
+    assert a.keys() == c.keys() and all(torch.equal(a[k], c[k]) for k in a)
+    # and a deeper sum widens it
+    a, d = kb.ln_slack(x, w, b, dy), kb.ln_slack(x, w, b, dy, depth=2 * n)
+    assert (d["mean"] > a["mean"]).all() and (d["dx"] > a["dx"]).all()
+
+
+@pytest.mark.parametrize("op,C", WAVE_CASES)
+@pytest.mark.parametrize("family", kb.ADD_NORM_FAMILIES)
+def test_kernel_order_add_norm_meets_bound(family, op, C):
+    """Every output of the wave-per-row kernels, evaluated in fp32 in their
+    lane layout, butterfly and column-sum order, with and without d_x_new."""
+    x, w, b, dy, dres = _wave_case(op, family, 5, C)
+    for r in (dres, None):
+        got = kb.emu_add_norm(op, x, w, b, dy, r)
+        kb.check_add_norm(op, got, x, w, b, dy, r, family,
+                          tag=f"add_{op}-emu")
+    if family in ("constant", "shifted"):
+        # the delta of add_norm_inputs reaches these rows exactly
+        t = kb.add_norm_inputs(op, family, 5, C)
+        for extra in (0.0, t["dbias"].float()):
+            x0 = (x.float() - t["delta"].float() - extra).bfloat16()
+            assert torch.equal(
+                (x0.float() + t["delta"].float() + extra).bfloat16(), x)
+
+
+@pytest.mark.parametrize("op,C", [("ln", 256), ("rms", 512)])
+def test_kernel_order_add_norm_meets_bound_over_the_row_loop(op, C):
+    """4099 rows on a grid of 1024 blocks: a lane adds two rows, the reducer
+    1024 partial rows; rows 4096 and 4098 carry 64 times the gradient."""
+    R = 4099
+    args = _wave_case(op, "randn2", R, C, sentinel=(R - 1, 4096))
+    got = kb.emu_add_norm(op, *args)
+    kb.check_add_norm(op, got, *args, "sentinel", tag=f"add_{op}-emu")
+
+
+@pytest.mark.parametrize("op,C", WAVE_CASES)
+def test_bound_rejects_dx_rounded_before_the_residual_add(op, C):
+    args = _wave_case(op, "dres_cancel", 5, C)
+    ref = kb.add_norm_formula(op, *args)
+    slack = kb.add_norm_slack(op, *args)
+    good = kb.emu_add_norm(op, *args)["dx_total"]
+    early = kb.emu_add_norm(op, *args, round_first=True)["dx_total"]
+    bad0, _ = kb.violations(good, ref["dx_total"], slack["dx_total"])
+    bad1, _ = kb.violations(early, ref["dx_total"], slack["dx_total"])
+    print(f"{op} C={C}: rounded first, {int(bad1.sum())} of {bad1.numel()} "
+          "outside")
+    assert not bad0.any() and bad1.sum() > bad1.numel() // 2
+    # the column sum of the residues notices too
+    if op == "ln":
+        dd = kb.emu_add_norm(op, *args, round_first=True)["ddbias"]
+        bad, _ = kb.violations(dd, ref["ddbias"], slack["ddbias"])
+        assert bad.sum() > C // 2
+
+
+def test_bound_rejects_the_reciprocal_of_another_width():
+    """1 / 1024 at C = 768 (LayerNorm), 1 / 4096 at C = 2048 (RMSNorm)."""
+    for op, C, wrong in (("ln", 768, 1024), ("rms", 2048, 4096)):
+        args = _wave_case(op, "randn2", 5, C)
+        assert _wave_judge(op, kb.emu_add_norm(op, *args), args, "randn2")
+        got = kb.emu_add_norm(op, *args, inv_c=1.0 / wrong)
+        for k in got.keys() - {"dbeta"}:   # dbeta is sum(dy): no 1 / C in it
+            assert not _wave_judge(op, {k: got[k]}, args, "1/C:" + k), k
+
+
+@pytest.mark.parametrize("C", WAVE_WIDTHS["ln"])
+def test_bound_rejects_one_pass_variance_in_wave_order(C):
+    """Held by the fp32 bound on rstd.  Through y the error shows only where
+    it exceeds the bf16 ulp y is allowed anyway: it does at C = 768 (rstd off
+    by several per cent), not at 256 and 1024, where the sums of squares
+    happen to stay nearly exact."""
+    args = _wave_case("ln", "shifted", 5, C)
+    ref = kb.add_norm_formula("ln", *args)["rstd"]
+    assert _wave_judge("ln", kb.emu_add_norm("ln", *args), args, "shifted")
+    got = kb.emu_add_norm("ln", *args, one_pass=True)
+    rel = float(((got["rstd"].double() - ref) / ref).abs().max())
+    print(f"C={C}: one-pass rstd off by {100 * rel:.3g} %")
+    assert not _wave_judge("ln", {"rstd": got["rstd"]}, args, "one-pass")
+    if C == 768:
+        for k in ("y", "dx_total"):
+            assert not _wave_judge("ln", {k: got[k]}, args, "one-pass:" + k)
+
+
+# RMSNorm at C = 4096 is left out: the sum of squares is 72 deep there and the
+# derived rstd slack (41 U = 2.4e-6 relative) is wider than what eps moves
+@pytest.mark.parametrize("op,C", [c for c in WAVE_CASES if c != ("rms", 4096)])
+def test_bound_rejects_dropped_eps_on_constant_rows(op, C):
+    """LayerNorm: the variance is exactly 0, so rstd is inf without eps.
+    RMSNorm: eps = 1e-5 against a mean square of 2.25 moves rstd of row 0 by
+    2.2e-6 relative."""
+    args = _wave_case(op, "constant", 5, C)
+    assert _wave_judge(op, kb.emu_add_norm(op, *args), args, "constant")
+    got = kb.emu_add_norm(op, *args, eps=0.0)
+    assert not _wave_judge(op, {"rstd": got["rstd"]}, args, "no-eps")
+    if op == "ln":
+        assert not _wave_judge(op, {"y": got["y"]}, args, "no-eps")
+
+
+@pytest.mark.parametrize("op,C", [("ln", 256), ("ln", 1024), ("rms", 512)])
+@pytest.mark.parametrize("weight", [0.0, 2.0], ids=["dropped", "doubled"])
+@pytest.mark.parametrize("R", [5, 4099])
+def test_bound_rejects_a_sentinel_row_dropped_or_doubled(R, weight, op, C):
+    last = R - 1
+    other = 4096 if R > 4096 else 2
+    args = _wave_case(op, "randn2", R, C, sentinel=(last, other))
+    sums = ("dgamma", "dbeta", "ddbias") if op == "ln" else ("dgamma",)
+    for r in (last, other):
+        rw = np.ones(R, np.float32)
+        rw[r] = weight
+        got = kb.emu_add_norm(op, *args, row_weight=rw)
+        ref = kb.add_norm_formula(op, *args)
+        slack = kb.add_norm_slack(op, *args)
+        for k in sums:
+            bad, _ = kb.violations(got[k], ref[k], slack[k])
+            assert bad.sum() > C // 2, (k, r, int(bad.sum()))
+
+
+@pytest.mark.parametrize("op,C", WAVE_CASES)
+def test_bound_rejects_dgamma_from_dy_times_w(op, C):
+    args = _wave_case(op, "randn2", 5, C)
+    ref = kb.add_norm_formula(op, *args)
+    slack = kb.add_norm_slack(op, *args)
+    got = kb.emu_add_norm(op, *args, dgamma_dyw=True)["dgamma"]
+    bad, _ = kb.violations(got, ref["dgamma"], slack["dgamma"])
+    assert bad.sum() > C // 2
 
 
 @pytest.mark.parametrize("dy_kind", ["ones", "pattern"])
