@@ -405,13 +405,19 @@ def bench_gqa_attn_hd128(out, rounds=7, iters=20):
     #   fwdbwd_sdpa    forward + backward of the SDPA call through autograd
     #   fwdbwd_gqa128  forward + backward of fused_causal_gqa_attention: our
     #                  forward, K/V expansion, the aten backward, the group sum
-    # FLOP: the causal half of 2 (forward) or 7 (both) B Hq T^2 D products.
+    #   bwd_aten128    the backward alone of that path, fed our forward's out
+    #                  and lse: K/V expansion, the aten backward, the group sums
+    #   bwd_gqa128     csrc/gqa_attn_hd128_bwd_kernels.hip on the same inputs
+    # FLOP: the causal half of 2 (forward), 5 (backward) or 7 (both)
+    # B Hq T^2 D products.
     import torch.nn.functional as F
     from torch.nn.attention import SDPBackend, sdpa_kernel
     from sharedtensor_amd.ops import fused_gqa_attn
+    from sharedtensor_amd.ops.fused_attn import _philox_state
     pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
            SDPBackend.MATH]
     Hq, Hkv, D = 32, 8, 128
+    G = Hq // Hkv
 
     def timed(fn):
         e0 = torch.cuda.Event(enable_timing=True)
@@ -442,12 +448,30 @@ def bench_gqa_attn_hd128(out, rounds=7, iters=20):
                 qr.grad = kr.grad = vr.grad = None
             return run
 
+        ot = o.transpose(1, 2)
+        gq, gk, gv = (torch.empty_like(x) for x in (q, k, v))
+        delta = torch.empty(B, Hq, T, dtype=torch.float32, device="cuda")
+        seed, offset = _philox_state()
+
+        def bwd_aten():  # _FusedCausalGqaAttnHd128.backward
+            ke, ve = (x.repeat_interleave(G, dim=1) for x in (k, v))
+            with sdpa_kernel(pri, set_priority=True):
+                _, dk, dv, _ = torch.ops.aten.\
+                    _scaled_dot_product_efficient_attention_backward(
+                        dout, q, ke, ve, None, ot, lse, seed, offset, 0.0,
+                        [True, True, True, False], True, scale=D ** -0.5)
+            for x in (dk, dv):
+                x.unflatten(1, (Hkv, G)).sum(2)
+
         arms = {
             "fwd_sdpa": sdpa,
             "fwd_gqa128": lambda: fused_gqa_attn.gqa_forward(q, k, v, out=o,
                                                              lse=lse),
             "fwdbwd_sdpa": fwd_bwd(sdpa),
             "fwdbwd_gqa128": fwd_bwd(fused_gqa_attn.fused_causal_gqa_attention),
+            "bwd_aten128": bwd_aten,
+            "bwd_gqa128": lambda: fused_gqa_attn.gqa_backward_hd128(
+                q, k, v, ot, lse, dout, None, gq, gk, gv, delta=delta),
         }
         for fn in arms.values():
             timed(fn)
@@ -460,13 +484,16 @@ def bench_gqa_attn_hd128(out, rounds=7, iters=20):
         for n, xs in ms.items():
             xs = sorted(xs)
             med = xs[len(xs) // 2]
-            mult = {"fwd": 2, "fwdbwd": 7}[n.split("_")[0]]
+            mult = {"fwd": 2, "bwd": 5, "fwdbwd": 7}[n.split("_")[0]]
             rec[n] = dict(ms_median=round(med, 4),
                           ms_range=[round(xs[0], 4), round(xs[-1], 4)],
                           tflops=round(mult * flop / med / 1e9, 1))
         rec["fwdbwd_gqa128_wholly_below_sdpa"] = (
             rec["fwdbwd_gqa128"]["ms_range"][1]
             < rec["fwdbwd_sdpa"]["ms_range"][0])
+        rec["bwd_gqa128_wholly_below_aten128"] = (
+            rec["bwd_gqa128"]["ms_range"][1]
+            < rec["bwd_aten128"]["ms_range"][0])
         out[f"gqa_attn_hd128_B{B}_T{T}"] = rec
 
 

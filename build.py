@@ -40,6 +40,7 @@ SOURCES = [
     "gqa_attn_kernels.hip",
     "gqa_attn_bwd_kernels.hip",
     "gqa_attn_hd128_kernels.hip",
+    "gqa_attn_hd128_bwd_kernels.hip",
     "wgrad_kernels.hip",
     "bindings.cpp",
 ]
@@ -60,11 +61,14 @@ HEADERS = ["attn_bwd_tile.h", "attn_fwd_tile.h", "attn_tile.h", "common.h", "cod
 # gqa_attn_bwd_kernels.hip shares that arithmetic and gets the same entry.
 # gqa_attn_hd128_kernels.hip, new and never run packed either, gets it for
 # the rescale of its 64 O registers per tile.
+# gqa_attn_hd128_bwd_kernels.hip has the dS arithmetic of the hd64 backward
+# files and is new and never run packed: the same entry.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "attn_bwd_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_bwd_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_hd128_kernels.hip": NO_PACKED_FP32,
+    "gqa_attn_hd128_bwd_kernels.hip": NO_PACKED_FP32,
 }
 
 

@@ -6,7 +6,9 @@
 // its HW = 1, G = 1 case), the half tile of the dK/dV kernels
 // (dkdv_half_tile) and the launchers' argument checks.  The header comment
 // of attn_bwd_kernels.hip derives the swizzle and the lane layouts.
-// Everything sits in an anonymous namespace: each kernel file gets its own
+// gqa_attn_hd128_bwd_kernels.hip (head dim 128) takes the swizzle, the two
+// read patterns and the checks from here, a 256-byte row being two 64-column
+// halves of this tile format.  Everything sits in an anonymous namespace: each kernel file gets its own
 // copy, inlined.
 #pragma once
 
@@ -423,11 +425,12 @@ __device__ __forceinline__ void dkdv_half_tile(
 
 // ------------------------------------------------------------------ host
 
-// no two rows of a (B, T, H, 64) output may overlap: with the dimensions of
+// no two rows of a (B, T, H, row) output may overlap: with the dimensions of
 // more than one element ordered by stride, the smallest stride covers a
-// 64-element row and every further one the whole extent of the dimension
+// `row`-element row and every further one the whole extent of the dimension
 // before it
-inline bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H) {
+inline bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H,
+                          int64_t row = kD) {
   const int64_t dims[3] = {B, T, H};
   int64_t sd[3][2];
   int n = 0;
@@ -441,7 +444,7 @@ inline bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H) {
       sd[j][0] = st[i];
       sd[j][1] = dims[i];
     }
-  int64_t need = kD;
+  int64_t need = row;
   for (int i = 0; i < n; ++i) {
     if (sd[i][0] < need) return false;
     need = sd[i][0] * sd[i][1];
@@ -450,7 +453,8 @@ inline bool rows_disjoint(const int64_t* st, int64_t B, int64_t T, int64_t H) {
 }
 
 // The checks both backward launchers make before they size their grids;
-// returns G = Hq / Hkv.  The MHA op passes Hq == Hkv and grouped = false.
+// returns G = Hq / Hkv.  The MHA op passes Hq == Hkv and grouped = false, the
+// head-dim-128 op row = 128.
 inline int64_t check_attn_bwd(
     const char* op, const void* q, const void* k, const void* v,
     const void* out, const void* dout, const float* lse, const void* dq,
@@ -458,7 +462,7 @@ inline int64_t check_attn_bwd(
     int64_t Hkv, int64_t T, const int64_t* qs, const int64_t* ks,
     const int64_t* vs, const int64_t* os, const int64_t* dos,
     const int64_t* dqs, const int64_t* dks, const int64_t* dvs,
-    int64_t lse_stride, float scale, bool grouped) {
+    int64_t lse_stride, float scale, bool grouped, int64_t row = kD) {
   const int64_t G =
       check_attn_problem(op, B, Hq, Hkv, T, lse_stride, scale, grouped);
   const void* ptrs[] = {q, k, v, out, dout, dq, dk, dv};
@@ -473,8 +477,9 @@ inline int64_t check_attn_bwd(
   check_align(lse, 4, op, "lse");
   check_align(delta, 4, op, "delta");
   check_attn_strides(op, {qs, ks, vs, os, dos, dqs, dks, dvs});
-  if (!rows_disjoint(dqs, B, T, Hq) || !rows_disjoint(dks, B, T, Hkv) ||
-      !rows_disjoint(dvs, B, T, Hkv))
+  if (!rows_disjoint(dqs, B, T, Hq, row) ||
+      !rows_disjoint(dks, B, T, Hkv, row) ||
+      !rows_disjoint(dvs, B, T, Hkv, row))
     throw std::runtime_error(std::string(op) + ": output rows would overlap");
   return G;
 }

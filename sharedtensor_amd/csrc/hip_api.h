@@ -421,6 +421,20 @@ void hip_gqa_attn_bwd_causal_hd64(
     const int64_t* dk_strides, const int64_t* dv_strides, int64_t lse_stride,
     float scale, hipStream_t s);
 
+// The same for head dim 128 (gqa_attn_hd128_bwd_kernels.hip): rows of 128
+// elements; every other rule and message is the hd64 launcher's.  The dK/dV
+// kernel takes 66048 B of dynamic LDS; the launcher raises the kernel's limit
+// once per device.
+void hip_gqa_attn_bwd_causal_hd128(
+    const void* q, const void* k, const void* v, const void* out,
+    const void* dout, const float* lse, void* dq, void* dk, void* dv,
+    float* delta, int64_t B, int64_t Hq, int64_t Hkv, int64_t T,
+    const int64_t* q_strides, const int64_t* k_strides,
+    const int64_t* v_strides, const int64_t* out_strides,
+    const int64_t* dout_strides, const int64_t* dq_strides,
+    const int64_t* dk_strides, const int64_t* dv_strides, int64_t lse_stride,
+    float scale, hipStream_t s);
+
 // Split-K bf16 weight gradient dW[N, K] = dY[M, N]^T X[M, K]
 // (wgrad_kernels.hip), fp32 accumulation.  ldy, ldx, ldw are row strides in
 // elements (multiples of 8, pointers 16-byte aligned).  `variant` picks the

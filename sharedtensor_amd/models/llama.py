@@ -44,6 +44,26 @@ FUSE_GQA_ATTN = True
 # head dim is 128.
 FUSE_GQA_ATTN_HD128 = True
 
+# Behind that forward, our own head-dim-128 backward
+# (csrc/gqa_attn_hd128_bwd_kernels.hip, ops.fused_gqa_attn.gqa_backward_hd128)
+# instead of the aten backward on expanded K/V.  It is consulted only when
+# head dim is 128 and FUSE_GQA_ATTN_HD128 took the call.  The flag is on only
+# if the own backward's range lies wholly below the aten arm's (expansion and
+# group sums included) at both benchmark shapes, Hq=32, Hkv=8, 7 rounds, arms
+# alternating in one call (benchmarks/bench_model_kernels.py
+# --only-gqa-attn-hd128, arms bwd_gqa128 and bwd_aten128), and the
+# `bench.py --model llama8b --batch 4 --seq 2048` step is faster than the
+# parent's.
+# Measured, range over 7 rounds: B=8, T=2048 backward 1.443-1.455 ms against
+# 1.741-1.747 ms for the aten arm; B=2, T=8192 4.180-4.309 ms against
+# 5.272-5.297 ms: wholly below at both shapes.  The llama8b step at
+# 4 x 2048 tokens, five steps per run, runs alternating: 403.4 and 404.2 ms
+# with the own backward against 402.2 and 404.1 ms for the parent's path.
+# That is 0.65 ms behind on the means and inside the spread, not lower, so
+# the flag is off.  Numbers in profiles/r18/.
+# SHTENS_FUSED_GQA_ATTN_HD128_BWD = 0 or 1 overrides it.
+FUSE_GQA_ATTN_HD128_BWD = False
+
 
 def _flag(env: str, default: bool) -> bool:
     v = os.environ.get(env)
@@ -184,7 +204,10 @@ class LlamaAttention(nn.Module):
             # q, k (rotated) and v (the (B, T, H, D).transpose(1, 2) view)
             # are read in place through their strides; K/V are not expanded
             from ..ops import fused_gqa_attn
-            y = fused_gqa_attn.fused_causal_gqa_attention(q, k, v)
+            own = q.shape[-1] == 128 and _flag(
+                "SHTENS_FUSED_GQA_ATTN_HD128_BWD", FUSE_GQA_ATTN_HD128_BWD)
+            y = fused_gqa_attn.fused_causal_gqa_attention(
+                q, k, v, own_backward_hd128=own)
         elif x.is_cuda:
             # same backend priority as GPT-2 (+16% measured; MATH fallback
             # covers shapes a backend rejects, e.g. GQA corner cases)

@@ -1,9 +1,10 @@
 """Causal bf16 grouped-query attention for head dim 64 with hand-written
 forward (csrc/gqa_attn_kernels.hip) and backward
 (csrc/gqa_attn_bwd_kernels.hip) kernels, and for head dim 128 with a
-hand-written forward (csrc/gqa_attn_hd128_kernels.hip): Hq = G * Hkv query
-heads, G in {2, 4, 8}, query head h reads kv head h // G (the ``enable_gqa``
-/ ``repeat_interleave`` convention).
+hand-written forward (csrc/gqa_attn_hd128_kernels.hip) and backward
+(csrc/gqa_attn_hd128_bwd_kernels.hip): Hq = G * Hkv query heads, G in
+{2, 4, 8}, query head h reads kv head h // G (the ``enable_gqa`` /
+``repeat_interleave`` convention).
 
 ``fused_causal_gqa_attention(q, k, v)`` takes q as a (B, Hq, T, 64) view and
 k, v as (B, Hkv, T, 64) views and reads them in place through their strides;
@@ -13,11 +14,13 @@ fp32.  The backward is ``gqa_backward``: two HIP kernels, dk and dv summed
 over the group in fp32 and rounded once, no atomics, bit-identical across
 repeats.
 
-At head dim 128 the same call runs our forward; its backward is the aten
-efficient-attention backward on q and on K and V expanded over the group,
-fed our ``out`` and ``lse`` (as ``fused_attn._FusedCausalAttn`` does for
-MHA), dk and dv summed over the group.  ``can_use_backward`` and
-``gqa_backward`` are head dim 64 only.
+At head dim 128 the same call runs our forward.  Its backward is by default
+the aten efficient-attention backward on q and on K and V expanded over the
+group, fed our ``out`` and ``lse`` (as ``fused_attn._FusedCausalAttn`` does
+for MHA), dk and dv summed over the group; with ``own_backward_hd128=True``
+it is ``gqa_backward_hd128``, which keeps the head dim 64 contract.
+``can_use_backward`` and ``gqa_backward`` are head dim 64 only,
+``can_use_backward_hd128`` and ``gqa_backward_hd128`` head dim 128 only.
 
 ``can_use`` says whether the kernels take the inputs; G = 1 is not theirs
 (ops/fused_attn.py has it).  A call outside ``can_use`` raises ``ValueError``;
@@ -34,7 +37,7 @@ from .fused_attn import (HEAD_DIM, _bth, _philox_state, _sdpa_priority,
                          _strides_ok)
 
 GROUPS = (2, 4, 8)
-HEAD_DIMS = (HEAD_DIM, 128)  # forward; the hand-written backward is HEAD_DIM
+HEAD_DIMS = (HEAD_DIM, 128)  # forward and backward; one backward entry each
 
 
 def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
@@ -91,36 +94,40 @@ def gqa_forward(q, k, v, scale=None, out=None, lse=None):
     return out, lse
 
 
+def _can_use_backward(q, k, v, out, lse, dout, D) -> bool:
+    if not can_use(q, k, v) or q.shape[-1] != D:
+        return False
+    for t in (out, dout):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16
+                and t.shape == q.shape and _strides_ok(t)):
+            return False
+    return (torch.is_tensor(lse) and lse.is_cuda
+            and lse.dtype == torch.float32
+            and lse.shape == q.shape[:3] and lse.is_contiguous())
+
+
 def can_use_backward(q, k, v, out, lse, dout) -> bool:
     """``can_use`` for the backward: q, k, v as there; out and dout bf16
     (B, Hq, T, 64) views under the same stride rules; lse contiguous
     (B, Hq, T) fp32.  Head dim 64 only."""
-    if not can_use(q, k, v) or q.shape[-1] != HEAD_DIM:
-        return False
-    for t in (out, dout):
-        if not (t.is_cuda and t.dtype == torch.bfloat16
-                and t.shape == q.shape and _strides_ok(t)):
-            return False
-    return (lse.is_cuda and lse.dtype == torch.float32
-            and lse.shape == q.shape[:3] and lse.is_contiguous())
+    return _can_use_backward(q, k, v, out, lse, dout, HEAD_DIM)
 
 
-def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
-                 dv=None, delta=None):
-    """dq (B, Hq, T, 64) and dk, dv (B, Hkv, T, 64) of ``gqa_forward`` on the
-    current stream, as views of contiguous (B, T, H, 64) bf16 buffers.  A
-    dout the kernel cannot read in place (a stride rule) is made contiguous
-    once; anything else outside ``can_use_backward`` raises.  ``dq``/``dk``/
-    ``dv`` (views to write into) and the fp32 (B, Hq, T) workspace ``delta``
-    may be passed in (tests put guard regions around them)."""
-    if (torch.is_tensor(dout) and dout.is_cuda and q.dim() == 4
-            and dout.dtype == torch.bfloat16 and dout.shape == q.shape
-            and not _strides_ok(dout)):
+def can_use_backward_hd128(q, k, v, out, lse, dout) -> bool:
+    """``can_use_backward`` for head dim 128, and for that alone."""
+    return _can_use_backward(q, k, v, out, lse, dout, 128)
+
+
+def _backward(D, launch, q, k, v, out, lse, dout, scale, dq, dk, dv, delta):
+    if (torch.is_tensor(dout) and torch.is_tensor(q) and dout.is_cuda
+            and q.dim() == 4 and dout.dtype == torch.bfloat16
+            and dout.shape == q.shape and not _strides_ok(dout)):
         dout = dout.contiguous()
-    if not can_use_backward(q, k, v, out, lse, dout):
+    if not _can_use_backward(q, k, v, out, lse, dout, D):
         raise ValueError("fused_gqa_attn: inputs the backward kernels do not "
-                         "take (see can_use_backward)")
-    B, Hq, T, D = q.shape
+                         "take (see can_use_backward"
+                         + ("" if D == HEAD_DIM else "_hd128") + ")")
+    B, Hq, T, _ = q.shape
     Hkv = k.shape[1]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
@@ -133,7 +140,7 @@ def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
                 or g.device != q.device or not _strides_ok(g)
                 or min(g.stride()[:3]) < D):
             raise ValueError("fused_gqa_attn: dq, dk, dv must be bf16 "
-                             "(B, H, T, 64) views the kernel can write")
+                             f"(B, H, T, {D}) views the kernel can write")
         grads.append(g)
     if delta is None:
         delta = torch.empty((B, Hq, T), dtype=torch.float32, device=q.device)
@@ -143,13 +150,34 @@ def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
                          "(B, Hq, T) fp32")
     dq, dk, dv = grads
     s = torch.cuda.current_stream(q.device).cuda_stream
-    _core.gqa_attn_bwd_causal_hd64(
+    launch(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
         dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
         dv.data_ptr(), delta.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k),
         _bth(v), _bth(out), _bth(dout), _bth(dq), _bth(dk), _bth(dv), T,
         float(scale), s)
     return dq, dk, dv
+
+
+def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
+                 dv=None, delta=None):
+    """dq (B, Hq, T, 64) and dk, dv (B, Hkv, T, 64) of ``gqa_forward`` on the
+    current stream, as views of contiguous (B, T, H, 64) bf16 buffers.  A
+    dout the kernel cannot read in place (a stride rule) is made contiguous
+    once; anything else outside ``can_use_backward`` raises.  ``dq``/``dk``/
+    ``dv`` (views to write into) and the fp32 (B, Hq, T) workspace ``delta``
+    may be passed in (tests put guard regions around them)."""
+    return _backward(HEAD_DIM, _core.gqa_attn_bwd_causal_hd64, q, k, v, out,
+                     lse, dout, scale, dq, dk, dv, delta)
+
+
+def gqa_backward_hd128(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
+                       dv=None, delta=None):
+    """``gqa_backward`` for head dim 128 (csrc/gqa_attn_hd128_bwd_kernels.hip)
+    under the same rules, with ``can_use_backward_hd128`` in the place of
+    ``can_use_backward`` and (B, T, H, 128) buffers."""
+    return _backward(128, _core.gqa_attn_bwd_causal_hd128, q, k, v, out, lse,
+                     dout, scale, dq, dk, dv, delta)
 
 
 class _FusedCausalGqaAttn(torch.autograd.Function):
@@ -196,14 +224,29 @@ class _FusedCausalGqaAttnHd128(torch.autograd.Function):
         return dq, dk, dv, None
 
 
-def fused_causal_gqa_attention(q, k, v, scale=None):
+class _FusedCausalGqaAttnHd128Own(_FusedCausalGqaAttnHd128):
+    """Our forward and our backward (``gqa_backward_hd128``)."""
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = gqa_backward_hd128(q, k, v, out, lse, dout, ctx.scale)
+        return dq, dk, dv, None
+
+
+def fused_causal_gqa_attention(q, k, v, scale=None, *,
+                               own_backward_hd128=False):
     """softmax(scale * q k^T + causal mask) v with grouped kv heads, for bf16
     q (B, Hq, T, D) and k, v (B, Hkv, T, D) views, D 64 or 128; returns
     (B, Hq, T, D) over a contiguous (B, T, Hq, D) buffer.  The backward is
-    ``gqa_backward`` at D = 64 and the aten efficient-attention backward on
-    expanded K/V at D = 128.  Inputs outside ``can_use`` raise."""
+    ``gqa_backward`` at D = 64; at D = 128 it is the aten efficient-attention
+    backward on expanded K/V, or ``gqa_backward_hd128`` with
+    ``own_backward_hd128=True`` (which D = 64 ignores).  Inputs outside
+    ``can_use`` raise."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if torch.is_tensor(q) and q.dim() == 4 and q.shape[-1] == 128:
-        return _FusedCausalGqaAttnHd128.apply(q, k, v, float(scale))
+        fn = (_FusedCausalGqaAttnHd128Own if own_backward_hd128
+              else _FusedCausalGqaAttnHd128)
+        return fn.apply(q, k, v, float(scale))
     return _FusedCausalGqaAttn.apply(q, k, v, float(scale))
