@@ -666,15 +666,19 @@ def bench_wgrad(out, rounds=7, iters=20, sweep=False):
         # the 256 x 256 variant against what it would replace: the library
         # call for the MLP shapes, variant 1 for the attention ones; for
         # mlp.fc also kernel + column sums against mm + dy.sum(0)
-        v256 = max(fw.COLSUM_VARIANTS)
+        # fused256p: the pipelined loop (variant 4)
+        v256, v256p = 3, 4
         arms["fused_v1"] = lambda: fw.wgrad(dy, x, out=dw, variant=1)
         arms["fused256"] = lambda: fw.wgrad(dy, x, out=dw, variant=v256)
+        arms["fused256p"] = lambda: fw.wgrad(dy, x, out=dw, variant=v256p)
         if name == "mlp_fc":
             db = torch.empty(N, dtype=torch.bfloat16, device="cuda")
             arms["torch_mm_sum0"] = lambda: (torch.mm(dyt, x, out=dw),
                                              torch.sum(dy, 0, out=db))
             arms["fused256_db"] = lambda: fw.wgrad(dy, x, out=dw,
                                                    variant=v256, db_out=db)
+            arms["fused256p_db"] = lambda: fw.wgrad(dy, x, out=dw,
+                                                    variant=v256p, db_out=db)
         for fn in arms.values():
             timed(fn)
         ms = {n: [] for n in arms}
@@ -697,6 +701,12 @@ def bench_wgrad(out, rounds=7, iters=20, sweep=False):
             rec["fused256_db_beats_torch_mm_sum0"] = bool(
                 rec["fused256_db"]["ms_median"]
                 < rec["torch_mm_sum0"]["ms_range"][0])
+        # variant 4 against what the shape had before it (profiles/r16/)
+        before = {"mlp_fc": "fused256_db", "attn_proj": "fused_v1"}.get(
+            name, "fused256")
+        mine = "fused256p_db" if name == "mlp_fc" else "fused256p"
+        rec["fused256p_beats_" + before] = bool(
+            rec[mine]["ms_median"] < rec[before]["ms_range"][0])
         out["wgrad_" + name] = rec
 
 

@@ -512,6 +512,354 @@ __global__ __launch_bounds__(256)
   }
 }
 
+// k_wgrad256 with a software-pipelined step loop: the same tile, split
+// scheme, swizzle, fragment layout, XCD remap and epilogue, and the same
+// MFMAs in the same order on every accumulator, so dW has the same bits
+// (tests/test_wgrad256p_resource_usage.py holds it to this plan).
+//   * global -> LDS without registers: 16-byte direct-to-LDS loads.  Such a
+//     load writes LDS at (wave-uniform base) + 16 lane, so the swizzle moves
+//     to the global side: the lane that lands on 16-byte slot s of token row
+//     r fetches chunk s ^ sw(r) of that row, where p_off(r, ch) = 256 r +
+//     16 (ch ^ sw(r)).  16 lanes still cover one contiguous 256-byte row
+//     segment, permuted.  One load of one wave fills 4 rows of one panel.
+//   * the LDS is a ring of R = 4 slots of 32 tokens (2 dY + 2 X half panels
+//     of [32][128], 32 KB; 128 KB in all).  Rows keep p_off: a slot is the
+//     upper or lower half of a k_wgrad256 stage, byte for byte.  Each slot is
+//     an array of its own, so that the compiler can tell a fragment read of
+//     one slot from a load landing in another and does not wait for it.
+//   * half step h (32 tokens, slot h % R) runs as: the 16 MFMAs of tokens
+//     0..15, under which the fragments of tokens 16..31 are read; then wait
+//     until this wave's loads of h + 1 have landed (a partial vmcnt: those of
+//     h + 2 stay in flight), barrier, issue the loads of h + R - 1 into the
+//     slot of h - 1, which every wave has left; then the 16 MFMAs of tokens
+//     16..31, under which the first fragments of h + 1 are read.  Loads are
+//     in flight for two half steps = one 64-token step, across two barriers.
+//     (As built today the compiler adds one full vmcnt wait per turn of the
+//     ring, so this holds for three half steps of four.)
+//   * NO LOAD PAST THE OPERANDS: a load of half step h is issued only under
+//     `h < hc` (hc = 2 s_count, workgroup-uniform), in the prologue and in
+//     the loop alike.  The last split ends at the last row of dY and X; a
+//     prefetch beyond hc would read past the end of the allocations.
+//   * CS: the workgroups of K-tile 0 read the dY half panels of the slot they
+//     are about to compute on back from LDS (a thread owns 8 columns of one
+//     panel and 4 of the 32 rows), sum in fp32 in a fixed order, and combine
+//     the 8 row groups through the first slot after the loop, as k_wgrad256.
+template <bool CS>
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(1, 1))) void k_wgrad256p(
+    const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
+    uint16_t* __restrict__ dw, float* __restrict__ ws,
+    uint16_t* __restrict__ db, float* __restrict__ wsb, int steps, int N,
+    int K, int64_t ldy, int64_t ldx, int64_t ldw, int split, int tiles_k,
+    int tiles) {
+  typedef __attribute__((address_space(3))) unsigned char lds_u8;
+  typedef const __attribute__((address_space(1))) void* gptr;
+  constexpr int NW = 4, NT = 64 * NW;
+  constexpr int BJ = 16 / NW;
+  constexpr int R = 4;                         // ring slots
+  constexpr int kHalf = 32;                    // tokens per slot
+  constexpr int kHPanel = kHalf * 256;         // a [32][128] half panel
+  constexpr int kSlot = 4 * kHPanel;
+  constexpr int kLoads = kSlot / (NT * 16);    // loads per thread and slot
+  static_assert(kLoads == 8 && kStep == 2 * kHalf, "ring plan");
+  __shared__ __attribute__((aligned(16))) unsigned char ring0[kSlot];
+  __shared__ __attribute__((aligned(16))) unsigned char ring1[kSlot];
+  __shared__ __attribute__((aligned(16))) unsigned char ring2[kSlot];
+  __shared__ __attribute__((aligned(16))) unsigned char ring3[kSlot];
+  auto slot = [&](auto s) -> lds_u8* {
+    constexpr int S = decltype(s)::value;
+    if constexpr (S == 0) return (lds_u8*)ring0;
+    else if constexpr (S == 1) return (lds_u8*)ring1;
+    else if constexpr (S == 2) return (lds_u8*)ring2;
+    else return (lds_u8*)ring3;
+  };
+
+  // block id -> (split, tile): ids that share an XCD become consecutive
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int xcd = orig % kXcd, q8 = nwg / kXcd, r8 = nwg % kXcd;
+  const int wg =
+      (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) +
+      orig / kXcd;
+  const int sp = wg / tiles, tile = wg % tiles;
+  const int n0 = (tile / tiles_k) * 256;
+  const int k0 = (tile % tiles_k) * 256;
+  const bool colsum = CS && k0 == 0;  // the same for the whole workgroup
+
+  const int sq = steps / split, sr = steps % split;
+  const int s_begin = sp * sq + min(sp, sr);
+  const int s_count = sq + (sp < sr ? 1 : 0);
+  const int hc = 2 * s_count;  // half steps; no load is issued for h >= hc
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int wn = wave / (NW / 2), wk = wave % (NW / 2);
+
+  // load i of a slot: half panel i >> 1 (dY 0, 1, X 0, 1), rows 16 (i & 1) +
+  // 4 wave .. + 3.  Lane l lands on row 4 wave + (l >> 4) of those 16, slot
+  // l & 15, and fetches the chunk that p_off puts there.
+  const int lrow = 4 * wave + (lane >> 4);
+  const int lch = (lane & 15) ^ (((lrow & 3) << 2) | ((lrow >> 2) & 3));
+  // uniform 64-bit base plus a 32-bit byte offset per thread, as k_wgrad256
+  const char* const ga =
+      reinterpret_cast<const char*>(dy + (int64_t)s_begin * kStep * ldy + n0);
+  const char* const gb =
+      reinterpret_cast<const char*>(x + (int64_t)s_begin * kStep * ldx + k0);
+  const uint32_t va = 2u * (uint32_t)(lrow * (int)ldy + 8 * lch);
+  const uint32_t vb = 2u * (uint32_t)(lrow * (int)ldx + 8 * lch);
+  // the callers test h < hc: see the header
+  auto dma = [&](lds_u8* base, int h) {
+    const int64_t t = (int64_t)h * kHalf;
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int p = i >> 1, r16 = 16 * (i & 1);
+      const char* g =
+          p < 2 ? ga + 2 * ((t + r16) * ldy + (p & 1) * kPanelCols) +
+                      (uint64_t)va
+                : gb + 2 * ((t + r16) * ldx + (p & 1) * kPanelCols) +
+                      (uint64_t)vb;
+      __builtin_amdgcn_global_load_lds(
+          (gptr)g, base + p * kHPanel + r16 * 256 + wave * 1024, 16, 0, 0);
+    }
+  };
+  // s_waitcnt with only vmcnt set (gfx9 encoding: vmcnt in bits 3:0 and
+  // 15:14, expcnt 6:4 and lgkmcnt 11:8 left at "no wait")
+#define SHAMD_WG_VMCNT(n) \
+  __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | 0x0f70)
+  // A bare barrier: the release fence of __syncthreads() would wait for every
+  // load in flight (they write LDS).  What must be ordered is ordered by
+  // hand: the vmcnt wait in front, and the reads of the slot that is loaded
+  // next were consumed by MFMAs issued before the barrier.  The scheduling
+  // barriers keep the compiler from moving LDS reads across it.  This rests
+  // on how the compiler treats these builtins (s_barrier has side effects,
+  // sched_barrier(0) lets nothing cross), not on a fence the LLVM memory
+  // model promises: reread the ISA of the loop after a compiler update
+  // (profiles/r19/README.md says what to look for).
+#define SHAMD_WG_BARRIER()                 \
+  do {                                     \
+    __builtin_amdgcn_sched_barrier(0);     \
+    __builtin_amdgcn_s_barrier();          \
+    __builtin_amdgcn_sched_barrier(0);     \
+  } while (0)
+  // one LDS read after every MFMA, 16 times
+#define SHAMD_WG_INTERLEAVE()                                   \
+  _Pragma("unroll") for (int q = 0; q < 16; ++q) {              \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          \
+  }
+
+  // column sums: thread owns chunk cs_ch of dY half panel cs_p, rows cs_r +
+  // 8 k of a slot
+  const int cs_ch = tid & 15, cs_p = (tid >> 4) & 1, cs_r = tid >> 5;
+  float c[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c[e] = 0.f;
+  // rows cs_r + 8 k: k and k + 2 share the swizzle, 16 rows apart
+  const int cs_off[2] = {cs_p * kHPanel + p_off(cs_r, cs_ch),
+                         cs_p * kHPanel + p_off(cs_r + 8, cs_ch)};
+  auto csum = [&](lds_u8* base) {
+#pragma unroll
+    for (int k = 0; k < kHalf / 8; ++k) {
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      const u32x4 q = *reinterpret_cast<
+          const __attribute__((address_space(3))) u32x4*>(
+          base + cs_off[k & 1] + (k >> 1) * (16 * 256));
+      float v[8];
+      unpack8(make_uint4(q[0], q[1], q[2], q[3]), v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) c[e] += v[e];
+    }
+  };
+
+  f32x16 acc[4][BJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < BJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+  // fragment addressing as in k_wgrad256; ss is 0 or 1 inside a slot
+  const int grp = lane >> 4, gi = lane & 15;
+  const int tr_q = gi >> 2, tr_p = gi & 3, hi = grp >> 1;
+  const int a_ch = 2 * (grp & 1) + (tr_p >> 1);
+  const int a_panel = wn * kHPanel;
+  const int b_panel = (2 + wk) * kHPanel;
+
+  // Byte offsets of the two reads of fragment i at tokens 0..15 of a slot,
+  // with the wave's half panel folded in; tokens 16..31 are 16 rows further.
+  // Kept as values so that slot, ss and nothing else become the immediate
+  // offset of a read: derived anew per read, the XOR forms took 88 address
+  // registers.
+  int a_off[4][2], b_off[BJ][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int o =
+          p_off(8 * jj + 4 * hi + tr_q, a_ch + 4 * i) + 8 * (tr_p & 1);
+      a_off[i][jj] = a_panel + o;
+      b_off[i][jj] = b_panel + o;
+    }
+  auto frag = [&](lds_u8* base, const int (&off)[2], int ss) -> bf16x8 {
+    bf16x8 f;
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      auto* a = reinterpret_cast<__attribute__((address_space(3))) s16x4*>(
+          base + off[jj] + ss * (16 * 256));
+      s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a);
+      bf16x4 tb = __builtin_bit_cast(bf16x4, tr);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[4 * jj + e] = tb[e];
+    }
+    return f;
+  };
+
+  // a[i] and b[0][j] hold the fragments of tokens 0..15 of the half step
+  // about to run; b[1][j] those of tokens 16..31
+  bf16x8 a[4], b[2][BJ];
+  auto half_step = [&](auto s, int h) {
+    constexpr int S = decltype(s)::value;
+    lds_u8* const cur = slot(std::integral_constant<int, S>{});
+    lds_u8* const nxt = slot(std::integral_constant<int, (S + 1) % R>{});
+    lds_u8* const fre = slot(std::integral_constant<int, (S + R - 1) % R>{});
+    if constexpr (CS) {
+      if (colsum) csum(cur);
+    }
+#pragma unroll
+    for (int j = 0; j < BJ; ++j) b[1][j] = frag(cur, b_off[j], 1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < BJ; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a[i], b[0][j], acc[i][j], 0, 0, 0);
+      a[i] = frag(cur, a_off[i], 1);
+    }
+    SHAMD_WG_INTERLEAVE();
+    // this wave's loads of h + 1 have landed; those of h + 2, if any, stay
+    // in flight.  Behind the barrier every wave's have, and every wave has
+    // left the slot of h - 1.  After the last half step nothing is in flight
+    // and the fragments read below are stale bytes of the ring, unused.
+    if (h + 2 < hc)
+      SHAMD_WG_VMCNT(kLoads);
+    else
+      SHAMD_WG_VMCNT(0);
+    SHAMD_WG_BARRIER();
+    if (h + R - 1 < hc) dma(fre, h + R - 1);
+#pragma unroll
+    for (int j = 0; j < BJ; ++j) b[0][j] = frag(nxt, b_off[j], 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < BJ; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a[i], b[1][j], acc[i][j], 0, 0, 0);
+      a[i] = frag(nxt, a_off[i], 0);
+    }
+    SHAMD_WG_INTERLEAVE();
+  };
+
+  // hc is the same for the whole workgroup: every barrier is reached by all
+  // of its waves or by none
+  if (hc > 0) {
+    using std::integral_constant;
+    // half steps 0 .. R - 2 into the slots from S0 on, each only if it
+    // exists, and the first fragments
+    auto prologue = [&](auto s0) {
+      constexpr int S0 = decltype(s0)::value;
+      lds_u8* const first = slot(integral_constant<int, S0>{});
+      dma(first, 0);
+      if (1 < hc) dma(slot(integral_constant<int, (S0 + 1) % R>{}), 1);
+      if (2 < hc) dma(slot(integral_constant<int, (S0 + 2) % R>{}), 2);
+      if (2 < hc)
+        SHAMD_WG_VMCNT(2 * kLoads);
+      else if (1 < hc)
+        SHAMD_WG_VMCNT(kLoads);
+      else
+        SHAMD_WG_VMCNT(0);
+      SHAMD_WG_BARRIER();
+#pragma unroll
+      for (int j = 0; j < BJ; ++j)
+        b[0][j] = frag(first, b_off[j], 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        a[i] = frag(first, a_off[i], 0);
+    };
+    // the loop body is one whole turn of the ring, two steps, without a
+    // branch around MFMAs (with one, the accumulators spilled); an odd step
+    // count runs its first step in slots 2 and 3
+    int h = 0;
+    if (s_count & 1) {
+      prologue(integral_constant<int, 2>{});
+      half_step(integral_constant<int, 2>{}, 0);
+      half_step(integral_constant<int, 3>{}, 1);
+      h = 2;
+    } else {
+      prologue(integral_constant<int, 0>{});
+    }
+    for (; h < hc; h += R) {
+      half_step(integral_constant<int, 0>{}, h);
+      half_step(integral_constant<int, 1>{}, h + 1);
+      half_step(integral_constant<int, 2>{}, h + 2);
+      half_step(integral_constant<int, 3>{}, h + 3);
+    }
+  }
+#undef SHAMD_WG_VMCNT
+#undef SHAMD_WG_BARRIER
+#undef SHAMD_WG_INTERLEAVE
+
+  // ---- epilogue, as in k_wgrad256
+#define SHAMD_WG_PIN(v) asm volatile("" : "+a"(v))
+  const int row0 = n0 + wn * 128 + 4 * (lane >> 5);
+  const int col0 = k0 + wk * (32 * BJ) + (lane & 31);
+  if (split == 1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < BJ; ++j) {
+        uint16_t* o = dw + (int64_t)(row0 + 32 * i) * ldw + col0 + 32 * j;
+        SHAMD_WG_PIN(acc[i][j]);
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          o[((e & 3) + 8 * (e >> 2)) * ldw] = f32_to_bf16(acc[i][j][e]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  } else {
+    float* out = ws + (int64_t)sp * N * K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < BJ; ++j) {
+        float* o = out + (int64_t)(row0 + 32 * i) * K + col0 + 32 * j;
+        SHAMD_WG_PIN(acc[i][j]);
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          o[(int64_t)((e & 3) + 8 * (e >> 2)) * K] = acc[i][j][e];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  }
+#undef SHAMD_WG_PIN
+
+  if constexpr (CS) {
+    if (colsum) {
+      // every wave has left the ring behind this barrier
+      __syncthreads();
+      float* red = reinterpret_cast<float*>(ring0);  // [kHalf / 4][256]
+      float* mine = red + cs_r * 256 + cs_p * 128 + 8 * cs_ch;
+      *reinterpret_cast<float4*>(mine) = make_float4(c[0], c[1], c[2], c[3]);
+      *reinterpret_cast<float4*>(mine + 4) =
+          make_float4(c[4], c[5], c[6], c[7]);
+      __syncthreads();
+      float s = red[tid];
+      for (int r = 1; r < NT / 32; ++r) s += red[r * 256 + tid];
+      if (split == 1)
+        db[n0 + tid] = f32_to_bf16(s);
+      else
+        wsb[(int64_t)sp * N + n0 + tid] = s;
+    }
+  }
+}
+
 // dW = bf16(sum over splits, in index order, of ws[split][N][K]); a thread
 // owns 8 consecutive columns of one row (K is a multiple of 8).  With db, the
 // blocks after those of dW do the same for db = bf16(sum of wsb[split][N]).
@@ -560,6 +908,7 @@ struct Variant {
 constexpr Variant kVariants[] = {{128, 128, false},
                                  {128, 128, false},
                                  {256, 128, false},
+                                 {256, 256, true},
                                  {256, 256, true}};
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
@@ -591,7 +940,8 @@ void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
   if (ldy < N || ldx < K || ldw < K) fail("row stride shorter than the row");
   if (ldy % 8 || ldx % 8 || ldw % 8)
     fail("row strides must be multiples of 8 elements");
-  // k_wgrad256 keeps a thread's byte offset inside 64 rows in 32 bits
+  // k_wgrad256 and k_wgrad256p keep a thread's byte offset inside 64 rows in
+  // 32 bits
   if (ldy > (1 << 24) || ldx > (1 << 24)) fail("row stride too large");
   check_align(dy, 16, op, "dy");
   check_align(x, 16, op, "x");
@@ -630,9 +980,16 @@ void hip_wgrad_bf16(const void* dy, const void* x, void* dw, float* ws,
     case 0: SHAMD_WGRAD_LAUNCH(1, 1, 2); break;
     case 1: SHAMD_WGRAD_LAUNCH(1, 1, 1); break;
     case 2: SHAMD_WGRAD_LAUNCH(2, 1, 2); break;
-    default:
+    case 3:
       dispatch_bool(db != nullptr, [&](auto cs) {
         k_wgrad256<decltype(cs)::value><<<grid, dim3(256), 0, s>>>(
+            dyp, xp, dwp, ws, dbp, wsb, (int)steps, (int)N, (int)K, ldy, ldx,
+            ldw, (int)split, tiles_k, (int)tiles);
+      });
+      break;
+    default:
+      dispatch_bool(db != nullptr, [&](auto cs) {
+        k_wgrad256p<decltype(cs)::value><<<grid, dim3(256), 0, s>>>(
             dyp, xp, dwp, ws, dbp, wsb, (int)steps, (int)N, (int)K, ldy, ldx,
             ldw, (int)split, tiles_k, (int)tiles);
       });

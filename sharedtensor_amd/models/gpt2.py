@@ -102,6 +102,9 @@ FUSE_QKV_ATTN_BWD = True
 # attn.qkv 0.289 ms against 0.302, mlp.proj 0.367 against 0.391 for the
 # library, and mlp.fc, whose bias gradient the same kernel takes from the dY
 # rows it stages, 0.361 against 0.462 for the library GEMM plus dy.sum(0).
+# The pipelined loop of the same tile (variant 4, profiles/r19/) took those
+# three from 0.299, 0.380 and 0.376 ms to 0.251, 0.322 and 0.348 in one
+# session, and attn.proj from 0.102 to 0.094.
 # lm_head (large output, tied weight) keeps aten.
 # SHTENS_FUSED_WGRAD = 0 or 1 overrides the flag for an A/B run.
 FUSE_WGRAD = True

@@ -39,18 +39,23 @@ NUM_CU = 256       # MI355X
 #      for 2 measured faster than for 3 (profiles/r09/)
 #   2: 256 x 128, 8 waves, two LDS stages (96 KB), 1 fits
 #   3: 256 x 256, 4 waves of 128 x 128, two LDS stages (128 KB), 1 fits
+#   4: the tile and arithmetic of 3 (dW has the same bits) with a pipelined
+#      step loop: direct-to-LDS loads into a ring of four 32-token slots
+#      (128 KB), in flight one 64-token step ahead
 VARIANTS = {0: (128, 128, 2), 1: (128, 128, 2), 2: (256, 128, 1),
-            3: (256, 256, 1)}
+            3: (256, 256, 1), 4: (256, 256, 1)}
 DEFAULT_VARIANT = 1
 # the variants that can write the column sums of dY (``db_out``)
-COLSUM_VARIANTS = frozenset({3})
+COLSUM_VARIANTS = frozenset({3, 4})
 
 # (N, K) of a weight -> variant, for the shapes whose microbenchmark beat what
 # they had before: the tuned library GEMM (profiles/r09/), or, for the
 # 256 x 256 variant (profiles/r16/), the library on the two MLP shapes and
-# variant 1 on attn.qkv.  attn.proj (9 tiles of 256 x 256, split 28) measured
-# slower with it and keeps variant 1.  models/gpt2.py routes only these
-TUNED: dict = {(768, 768): 1, (2304, 768): 3, (3072, 768): 3, (768, 3072): 3}
+# variant 1 on attn.qkv.  The pipelined loop of variant 4 (profiles/r19/)
+# beat variant 3 on those three, mlp.fc with its column sums included, and
+# variant 1 on attn.proj (9 tiles of 256 x 256, split 28), where variant 3
+# had lost.  models/gpt2.py routes only these
+TUNED: dict = {(768, 768): 4, (2304, 768): 4, (3072, 768): 4, (768, 3072): 4}
 
 
 def split_ranges(steps: int, split: int) -> List[Tuple[int, int]]:
