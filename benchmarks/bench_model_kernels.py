@@ -497,6 +497,82 @@ def bench_gqa_attn_hd128(out, rounds=7, iters=20):
         out[f"gqa_attn_hd128_B{B}_T{T}"] = rec
 
 
+def bench_gqa_attn_doc(out, rounds=7, iters=20):
+    # ---- document-masked grouped-query attention (packed batches) at B=64,
+    # Hq=32, Hkv=8, T=1024, D=64, q/k/v in the model's layout.  All arms in
+    # one interleaved, device-event timed run:
+    #   plain      the plain causal kernels (no document mask)
+    #   idle       the document kernels with one document per row: what the
+    #              mask machinery costs when it has nothing to mask
+    #   doc        the document kernels, documents of mean length 256
+    #   sdpa_mask  SDPA with the dense (B, 1, T, T) boolean mask of the same
+    #              documents, the route a packed batch had before; its
+    #              backward is forward + backward minus forward
+    # `doc_below_sdpa_mask`: the doc arm's forward + backward range lies
+    # wholly below the SDPA arm's, the condition of llama.FUSE_GQA_ATTN_DOC.
+    import torch.nn.functional as F
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from sharedtensor_amd.ops import fused_gqa_attn as fg
+    pri = [SDPBackend.EFFICIENT_ATTENTION, SDPBackend.FLASH_ATTENTION,
+           SDPBackend.MATH]
+    B, Hq, Hkv, T, D = 64, 32, 8, 1024, 64
+    mk = lambda h: torch.randn(B, T, h, D, device="cuda").to(
+        torch.bfloat16).transpose(1, 2)
+    q, k, v, dout = mk(Hq), mk(Hkv), mk(Hkv), mk(Hq)
+    gen = torch.Generator().manual_seed(0)
+    ids = torch.zeros(B, T, dtype=torch.long)
+    for b in range(B):  # lengths uniform in 1..511: mean 256
+        cuts = torch.randint(1, 512, (T,), generator=gen).cumsum(0)
+        ids[b] = torch.bucketize(torch.arange(T), cuts, right=True)
+    ids = ids.cuda()
+    one = fg.doc_start_end(torch.zeros_like(ids))
+    many = fg.doc_start_end(ids)
+    mask = ((ids[:, :, None] == ids[:, None, :])
+            & torch.ones(T, T, device="cuda", dtype=torch.bool).tril())[:, None]
+    o, lse = fg.gqa_forward(q, k, v)
+    ot = o.transpose(1, 2)
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(B, Hq, T, dtype=torch.float32, device="cuda")
+    qr, kr, vr = (x.detach().clone().requires_grad_() for x in (q, k, v))
+
+    def sdpa(x=q, y=k, z=v):
+        with sdpa_kernel(pri, set_priority=True):
+            return F.scaled_dot_product_attention(x, y, z, attn_mask=mask,
+                                                  enable_gqa=True)
+
+    def sdpa_fwd_bwd():
+        sdpa(qr, kr, vr).backward(dout)
+        qr.grad = kr.grad = vr.grad = None
+
+    def fwd(doc):
+        return lambda: fg.gqa_forward(q, k, v, out=o, lse=lse,
+                                      doc_start=doc and doc[0])
+
+    def bwd(doc):
+        kw = dict(doc_start=doc[0], doc_end=doc[1]) if doc else {}
+        return lambda: fg.gqa_backward(q, k, v, ot, lse, dout, None, gq, gk,
+                                       gv, delta=delta, **kw)
+
+    # the timed backwards read the plain forward's out and lse: the work per
+    # tile does not depend on the values
+    ms = _interleaved({
+        "fwd_plain": fwd(None), "fwd_idle": fwd(one), "fwd_doc": fwd(many),
+        "fwd_sdpa_mask": sdpa,
+        "bwd_plain": bwd(None), "bwd_idle": bwd(one), "bwd_doc": bwd(many),
+        "fwdbwd_sdpa_mask": sdpa_fwd_bwd}, rounds, iters)
+    ms["fwdbwd_doc"] = sorted(a + b for a, b in zip(ms["fwd_doc"],
+                                                    ms["bwd_doc"]))
+    rec = dict(B=B, Hq=Hq, Hkv=Hkv, T=T, D=D, rounds=rounds, iters=iters,
+               docs_per_row=round((ids.max(1).values + 1).float().mean().item(),
+                                  2))
+    for n, xs in ms.items():
+        rec[n] = dict(ms_median=round(xs[len(xs) // 2], 4),
+                      ms_range=[round(xs[0], 4), round(xs[-1], 4)])
+    rec["doc_below_sdpa_mask"] = bool(
+        ms["fwdbwd_doc"][-1] < ms["fwdbwd_sdpa_mask"][0])
+    out[f"gqa_attn_doc_B{B}_T{T}"] = rec
+
+
 def _interleaved(arms, rounds, iters):
     """Device-event time per call of each arm: one warm pass, then `rounds`
     rounds of `iters` calls, arms interleaved.  {arm: sorted ms}."""
@@ -736,6 +812,10 @@ def main():
         return
     if "--only-gqa-attn-hd128" in sys.argv[1:]:
         bench_gqa_attn_hd128(out)
+        print(json.dumps(out, indent=1))
+        return
+    if "--only-gqa-attn-doc" in sys.argv[1:]:
+        bench_gqa_attn_doc(out)
         print(json.dumps(out, indent=1))
         return
     if "--only-wgrad" in sys.argv[1:]:

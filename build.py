@@ -41,6 +41,8 @@ SOURCES = [
     "gqa_attn_bwd_kernels.hip",
     "gqa_attn_hd128_kernels.hip",
     "gqa_attn_hd128_bwd_kernels.hip",
+    "gqa_attn_doc_kernels.hip",
+    "gqa_attn_doc_bwd_kernels.hip",
     "wgrad_kernels.hip",
     "bindings.cpp",
 ]
@@ -63,12 +65,15 @@ HEADERS = ["attn_bwd_tile.h", "attn_fwd_tile.h", "attn_tile.h", "common.h", "cod
 # the rescale of its 64 O registers per tile.
 # gqa_attn_hd128_bwd_kernels.hip has the dS arithmetic of the hd64 backward
 # files and is new and never run packed: the same entry.
+# gqa_attn_doc_bwd_kernels.hip is the hd64 backward with a document mask, new
+# and never run packed: the same entry.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "attn_bwd_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_bwd_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_hd128_kernels.hip": NO_PACKED_FP32,
     "gqa_attn_hd128_bwd_kernels.hip": NO_PACKED_FP32,
+    "gqa_attn_doc_bwd_kernels.hip": NO_PACKED_FP32,
 }
 
 

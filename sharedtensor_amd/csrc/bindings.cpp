@@ -603,6 +603,63 @@ PYBIND11_MODULE(_core, m) {
         py::arg("dv_strides"), py::arg("lse_stride"), py::arg("scale"),
         py::arg("stream"));
 
+  // the same with a document mask (packed batches), head dim 64
+  m.def("gqa_attn_fwd_doc_hd64",
+        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t doc_start,
+           uintptr_t out, uintptr_t lse, int64_t B, int64_t Hq, int64_t Hkv,
+           int64_t T, Strides3 q_strides, Strides3 k_strides,
+           Strides3 v_strides, int64_t lse_stride, double scale,
+           uintptr_t stream) {
+          hip_gqa_attn_fwd_doc_hd64(
+              reinterpret_cast<const void*>(q),
+              reinterpret_cast<const void*>(k),
+              reinterpret_cast<const void*>(v),
+              reinterpret_cast<const int32_t*>(doc_start),
+              reinterpret_cast<void*>(out), reinterpret_cast<float*>(lse), B,
+              Hq, Hkv, T, q_strides.data(), k_strides.data(),
+              v_strides.data(), lse_stride, static_cast<float>(scale),
+              reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("doc_start"),
+        py::arg("out"), py::arg("lse"), py::arg("B"), py::arg("Hq"),
+        py::arg("Hkv"), py::arg("T"), py::arg("q_strides"),
+        py::arg("k_strides"), py::arg("v_strides"), py::arg("lse_stride"),
+        py::arg("scale"), py::arg("stream"));
+  m.def("gqa_attn_bwd_doc_hd64",
+        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out,
+           uintptr_t dout, uintptr_t lse, uintptr_t doc_start,
+           uintptr_t doc_end, uintptr_t dq, uintptr_t dk, uintptr_t dv,
+           uintptr_t delta, int64_t B, int64_t Hq, int64_t Hkv, int64_t T,
+           Strides3 q_strides, Strides3 k_strides, Strides3 v_strides,
+           Strides3 out_strides, Strides3 dout_strides, Strides3 dq_strides,
+           Strides3 dk_strides, Strides3 dv_strides, int64_t lse_stride,
+           double scale, uintptr_t stream) {
+          hip_gqa_attn_bwd_doc_hd64(
+              reinterpret_cast<const void*>(q),
+              reinterpret_cast<const void*>(k),
+              reinterpret_cast<const void*>(v),
+              reinterpret_cast<const void*>(out),
+              reinterpret_cast<const void*>(dout),
+              reinterpret_cast<const float*>(lse),
+              reinterpret_cast<const int32_t*>(doc_start),
+              reinterpret_cast<const int32_t*>(doc_end),
+              reinterpret_cast<void*>(dq), reinterpret_cast<void*>(dk),
+              reinterpret_cast<void*>(dv), reinterpret_cast<float*>(delta), B,
+              Hq, Hkv, T, q_strides.data(), k_strides.data(),
+              v_strides.data(), out_strides.data(), dout_strides.data(),
+              dq_strides.data(), dk_strides.data(), dv_strides.data(),
+              lse_stride, static_cast<float>(scale),
+              reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
+        py::arg("dout"), py::arg("lse"), py::arg("doc_start"),
+        py::arg("doc_end"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("delta"), py::arg("B"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("T"), py::arg("q_strides"), py::arg("k_strides"),
+        py::arg("v_strides"), py::arg("out_strides"), py::arg("dout_strides"),
+        py::arg("dq_strides"), py::arg("dk_strides"), py::arg("dv_strides"),
+        py::arg("lse_stride"), py::arg("scale"), py::arg("stream"));
+
   // split-K bf16 weight gradient dW = dY^T X
   m.def("wgrad_num_variants", &hip_wgrad_num_variants);
   m.def("wgrad_tile", [](int variant) {

@@ -435,6 +435,30 @@ void hip_gqa_attn_bwd_causal_hd128(
     const int64_t* dk_strides, const int64_t* dv_strides, int64_t lse_stride,
     float scale, hipStream_t s);
 
+// Document-masked causal bf16 grouped-query attention, head dim 64
+// (gqa_attn_doc_kernels.hip, gqa_attn_doc_bwd_kernels.hip): the hd64 ops
+// above with one more mask.  `doc_start` and `doc_end` are contiguous (B, T)
+// int32, the first position and one past the last position of the document
+// that holds position t, both non-decreasing in t; query i sees key j when
+// doc_start[b, i] <= j <= i.  Every other rule and message is the plain hd64
+// launchers'.
+void hip_gqa_attn_fwd_doc_hd64(const void* q, const void* k, const void* v,
+                               const int32_t* doc_start, void* out, float* lse,
+                               int64_t B, int64_t Hq, int64_t Hkv, int64_t T,
+                               const int64_t* q_strides,
+                               const int64_t* k_strides,
+                               const int64_t* v_strides, int64_t lse_stride,
+                               float scale, hipStream_t s);
+void hip_gqa_attn_bwd_doc_hd64(
+    const void* q, const void* k, const void* v, const void* out,
+    const void* dout, const float* lse, const int32_t* doc_start,
+    const int32_t* doc_end, void* dq, void* dk, void* dv, float* delta,
+    int64_t B, int64_t Hq, int64_t Hkv, int64_t T, const int64_t* q_strides,
+    const int64_t* k_strides, const int64_t* v_strides,
+    const int64_t* out_strides, const int64_t* dout_strides,
+    const int64_t* dq_strides, const int64_t* dk_strides,
+    const int64_t* dv_strides, int64_t lse_stride, float scale, hipStream_t s);
+
 // Split-K bf16 weight gradient dW[N, K] = dY[M, N]^T X[M, K]
 // (wgrad_kernels.hip), fp32 accumulation.  ldy, ldx, ldw are row strides in
 // elements (multiples of 8, pointers 16-byte aligned).  `variant` picks the

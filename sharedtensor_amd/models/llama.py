@@ -64,6 +64,23 @@ FUSE_GQA_ATTN_HD128 = True
 # SHTENS_FUSED_GQA_ATTN_HD128_BWD = 0 or 1 overrides it.
 FUSE_GQA_ATTN_HD128_BWD = False
 
+# Packed batches (`Llama.forward(idx, targets, doc_ids)`): attention masked
+# across document boundaries in our own kernels
+# (csrc/gqa_attn_doc_kernels.hip, csrc/gqa_attn_doc_bwd_kernels.hip: bf16,
+# head dim 64, G in {2, 4, 8}), which skip the tiles outside a row's
+# document, instead of SDPA with a dense (B, 1, T, T) boolean mask.  It is
+# consulted only when doc_ids is given, head dim is 64 and FUSE_GQA_ATTN took
+# the call.  The flag stays on only if the document arm's range over 7 rounds
+# lies wholly below the dense-mask SDPA arm's at B=64, Hq=32, Hkv=8, T=1024,
+# documents of mean length 256 (benchmarks/bench_model_kernels.py
+# --only-gqa-attn-doc).  Measured there (4.4 documents per row): forward +
+# backward 1.213-1.217 ms (0.381 + 0.833 ms medians) against 40.77-40.83 ms
+# for the SDPA call, and against 0.715 + 1.558 ms for the plain causal
+# kernels on the same shape, so it is on.  With one document per row the
+# document kernels take 0.675 + 1.612 ms.  Numbers in profiles/r20/.
+# SHTENS_FUSED_GQA_ATTN_DOC = 0 or 1 overrides it.
+FUSE_GQA_ATTN_DOC = True
+
 
 def _flag(env: str, default: bool) -> bool:
     v = os.environ.get(env)
@@ -184,7 +201,36 @@ class LlamaAttention(nn.Module):
         self.wv = nn.Linear(cfg.dim, cfg.n_kv_head * self.head_dim, bias=False)
         self.wo = nn.Linear(cfg.n_head * self.head_dim, cfg.dim, bias=False)
 
-    def forward(self, x, cos, sin):
+    def _doc_attention(self, q, k, v, doc_ids, doc_bounds):
+        """Causal attention inside each document of a packed row: the
+        document-masked kernels where they take the call, SDPA with the
+        dense boolean mask everywhere else (CPU, fp32, head dim 128, a flag
+        off)."""
+        from ..ops import fused_gqa_attn
+        if doc_bounds is None:
+            doc_bounds = fused_gqa_attn.doc_start_end(doc_ids)
+        if q.shape[-1] == 64 and _gqa_ok(q, k, v) \
+                and _flag("SHTENS_FUSED_GQA_ATTN_DOC", FUSE_GQA_ATTN_DOC):
+            return fused_gqa_attn.fused_causal_gqa_attention(
+                q, k, v, doc_bounds=doc_bounds)
+        pos = torch.arange(q.shape[2], device=q.device)
+        mask = ((pos >= doc_bounds[0][:, :, None])
+                & (pos <= pos[:, None])).unsqueeze(1)  # (B, 1, T, T)
+        gqa = self.n_kv != self.n_head
+        if not q.is_cuda:
+            return F.scaled_dot_product_attention(q, k, v, attn_mask=mask,
+                                                  enable_gqa=gqa)
+        from torch.nn.attention import SDPBackend, sdpa_kernel
+        with sdpa_kernel([SDPBackend.EFFICIENT_ATTENTION,
+                          SDPBackend.FLASH_ATTENTION, SDPBackend.MATH],
+                         set_priority=True):
+            return F.scaled_dot_product_attention(q, k, v, attn_mask=mask,
+                                                  enable_gqa=gqa)
+
+    def forward(self, x, cos, sin, doc_ids=None, doc_bounds=None):
+        """``doc_ids`` (B, T), or ``doc_bounds`` =
+        ``fused_gqa_attn.doc_start_end(doc_ids)`` built once for all layers,
+        masks attention across the documents of a packed row."""
         B, T, _ = x.shape
         q = self.wq(x).view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = self.wk(x).view(B, T, self.n_kv, self.head_dim).transpose(1, 2)
@@ -200,7 +246,9 @@ class LlamaAttention(nn.Module):
         if not fused:
             q = apply_rope(q, cos, sin)
             k = apply_rope(k, cos, sin)
-        if _gqa_ok(q, k, v):
+        if doc_ids is not None or doc_bounds is not None:
+            y = self._doc_attention(q, k, v, doc_ids, doc_bounds)
+        elif _gqa_ok(q, k, v):
             # q, k (rotated) and v (the (B, T, H, D).transpose(1, 2) view)
             # are read in place through their strides; K/V are not expanded
             from ..ops import fused_gqa_attn
@@ -252,14 +300,16 @@ class LlamaBlock(nn.Module):
         self.mlp_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.mlp = LlamaMLP(cfg)
 
-    def forward(self, x, cos, sin, delta=None):
+    def forward(self, x, cos, sin, delta=None, doc_bounds=None):
         """Takes the residual stream and the previous block's MLP output not
         yet added to it; returns the same pair, so every residual add
         happens inside the RMSNorm that follows it.  With ``delta=None``
         this is ``x = x + attn(attn_norm(x))`` and the caller owes
-        ``x + m`` for the MLP."""
+        ``x + m`` for the MLP.  ``doc_bounds``: see LlamaAttention."""
         x, h = add_rms(self.attn_norm, x, delta)
-        x, h = add_rms(self.mlp_norm, x, self.attn(h, cos, sin))
+        a = self.attn(h, cos, sin) if doc_bounds is None \
+            else self.attn(h, cos, sin, doc_bounds=doc_bounds)
+        x, h = add_rms(self.mlp_norm, x, a)
         return x, self.mlp(h)
 
 
@@ -286,12 +336,22 @@ class Llama(nn.Module):
             self._rope = (cos, sin)
         return self._rope
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, doc_ids=None):
+        """``doc_ids`` (B, T), equal values in contiguous runs: a packed
+        batch, attention masked across its document boundaries.  RoPE
+        positions stay the absolute positions of the row."""
         x = self.tok(idx)
         cos, sin = self._rope_cache(idx.device, x.dtype)
         delta = None
+        bounds = None
+        if doc_ids is not None:
+            if doc_ids.shape != idx.shape:
+                raise ValueError("doc_ids must have the shape of idx")
+            from ..ops import fused_gqa_attn
+            bounds = fused_gqa_attn.doc_start_end(doc_ids)  # once, all layers
         for blk in self.blocks:
-            x, delta = blk(x, cos, sin, delta)
+            x, delta = blk(x, cos, sin, delta) if bounds is None \
+                else blk(x, cos, sin, delta, doc_bounds=bounds)
         _, x = add_rms(self.norm, x, delta)  # absorbs the last add
         logits = self.lm_head(x)
         if targets is None:

@@ -22,6 +22,14 @@ it is ``gqa_backward_hd128``, which keeps the head dim 64 contract.
 ``can_use_backward`` and ``gqa_backward`` are head dim 64 only,
 ``can_use_backward_hd128`` and ``gqa_backward_hd128`` head dim 128 only.
 
+With ``doc_ids`` (a (B, T) integer tensor whose equal values form contiguous
+runs, one run per document of a packed batch row) query i sees key j only if
+j <= i and both lie in the same document.  The mask is two int32 (B, T)
+arrays from ``doc_start_end``, never a T x T object, and the kernels
+(csrc/gqa_attn_doc_kernels.hip, csrc/gqa_attn_doc_bwd_kernels.hip) skip the
+tiles outside a row's document.  Head dim 64 only; at head dim 128 the call
+raises.  ``doc_ids=None`` is the plain causal path, untouched.
+
 ``can_use`` says whether the kernels take the inputs; G = 1 is not theirs
 (ops/fused_attn.py has it).  A call outside ``can_use`` raises ``ValueError``;
 there is never a silent fall-back.
@@ -40,10 +48,52 @@ GROUPS = (2, 4, 8)
 HEAD_DIMS = (HEAD_DIM, 128)  # forward and backward; one backward entry each
 
 
-def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
+def doc_start_end(doc_ids: torch.Tensor):
+    """(doc_start, doc_end) of a packed batch: int32 (B, T), the first
+    position and one past the last position of the document that holds t,
+    both non-decreasing in t.  ``doc_ids`` is a (B, T) integer tensor whose
+    equal values form contiguous runs; anything else raises ``ValueError``
+    (the check reads one flag back from the device)."""
+    if not (torch.is_tensor(doc_ids) and doc_ids.dim() == 2
+            and doc_ids.numel() > 0 and not doc_ids.dtype.is_floating_point
+            and not doc_ids.dtype.is_complex
+            and doc_ids.dtype != torch.bool):
+        raise ValueError("fused_gqa_attn: doc_ids must be a non-empty (B, T) "
+                         "integer tensor")
+    B, T = doc_ids.shape
+    pos = torch.arange(T, dtype=torch.int32, device=doc_ids.device)
+    first = torch.ones((B, T), dtype=torch.bool, device=doc_ids.device)
+    first[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+    # as many runs as distinct values, or a value comes back after a gap
+    ids = doc_ids.sort(dim=1).values
+    distinct = 1 + (ids[:, 1:] != ids[:, :-1]).sum(1)
+    if not bool((first.sum(1) == distinct).all()):
+        raise ValueError("fused_gqa_attn: equal doc_ids must form contiguous "
+                         "runs")
+    start = torch.where(first, pos, 0).cummax(dim=1).values
+    last = first.roll(-1, dims=1)  # column 0 is True: T - 1 ends a document
+    end = torch.where(last, pos + 1, T).flip(1).cummin(dim=1).values.flip(1)
+    return start.int().contiguous(), end.int().contiguous()
+
+
+def _doc_ok(t, B, T, device) -> bool:
+    return (torch.is_tensor(t) and t.dtype == torch.int32
+            and t.shape == (B, T) and t.is_contiguous() and t.device == device)
+
+
+def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+            doc_start=None, doc_end=None) -> bool:
     """q: (B, Hq, T, D); k, v: (B, Hkv, T, D), D 64 or 128.  True for CUDA
     bf16, Hq a multiple of Hkv by 2, 4 or 8, equal batch and length, a
-    non-empty problem, and the stride rules of ``fused_attn.can_use``."""
+    non-empty problem, and the stride rules of ``fused_attn.can_use``.  With
+    ``doc_start`` (and, for the backward, ``doc_end``) also: D = 64 and
+    contiguous int32 (B, T) arrays on q's device."""
+    if doc_start is not None or doc_end is not None:
+        if not can_use(q, k, v) or q.shape[-1] != HEAD_DIM:
+            return False
+        B, _, T, _ = q.shape
+        return (_doc_ok(doc_start, B, T, q.device)
+                and (doc_end is None or _doc_ok(doc_end, B, T, q.device)))
     if not (q.is_cuda and k.is_cuda and v.is_cuda):
         return False
     if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
@@ -61,11 +111,13 @@ def can_use(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     return _strides_ok(q) and _strides_ok(k) and _strides_ok(v)
 
 
-def gqa_forward(q, k, v, scale=None, out=None, lse=None):
+def gqa_forward(q, k, v, scale=None, out=None, lse=None, doc_start=None):
     """Launch the kernel on the current stream.  Returns (out, lse): out
     (B, T, Hq, D) bf16 contiguous, D 64 or 128, lse (B, Hq, T) fp32.
-    ``out``/``lse`` may be passed in (tests put guard regions around them)."""
-    if not can_use(q, k, v):
+    ``out``/``lse`` may be passed in (tests put guard regions around them).
+    With ``doc_start`` (of ``doc_start_end``) it is the document-masked
+    kernel, head dim 64 only."""
+    if not can_use(q, k, v, doc_start):
         raise ValueError("fused_gqa_attn: inputs the kernel does not take "
                          "(see can_use)")
     B, Hq, T, D = q.shape
@@ -85,6 +137,12 @@ def gqa_forward(q, k, v, scale=None, out=None, lse=None):
         raise ValueError("fused_gqa_attn: lse must be contiguous (B, Hq, T) "
                          "fp32")
     s = torch.cuda.current_stream(q.device).cuda_stream
+    if doc_start is not None:
+        _core.gqa_attn_fwd_doc_hd64(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), doc_start.data_ptr(),
+            out.data_ptr(), lse.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k),
+            _bth(v), T, float(scale), s)
+        return out, lse
     launch = (_core.gqa_attn_fwd_causal_hd64 if D == HEAD_DIM
               else _core.gqa_attn_fwd_causal_hd128)
     launch(
@@ -118,12 +176,14 @@ def can_use_backward_hd128(q, k, v, out, lse, dout) -> bool:
     return _can_use_backward(q, k, v, out, lse, dout, 128)
 
 
-def _backward(D, launch, q, k, v, out, lse, dout, scale, dq, dk, dv, delta):
+def _backward(D, launch, q, k, v, out, lse, dout, scale, dq, dk, dv, delta,
+              doc=()):
     if (torch.is_tensor(dout) and torch.is_tensor(q) and dout.is_cuda
             and q.dim() == 4 and dout.dtype == torch.bfloat16
             and dout.shape == q.shape and not _strides_ok(dout)):
         dout = dout.contiguous()
-    if not _can_use_backward(q, k, v, out, lse, dout, D):
+    if not _can_use_backward(q, k, v, out, lse, dout, D) \
+            or (doc and (doc[1] is None or not can_use(q, k, v, *doc))):
         raise ValueError("fused_gqa_attn: inputs the backward kernels do not "
                          "take (see can_use_backward"
                          + ("" if D == HEAD_DIM else "_hd128") + ")")
@@ -152,21 +212,28 @@ def _backward(D, launch, q, k, v, out, lse, dout, scale, dq, dk, dv, delta):
     s = torch.cuda.current_stream(q.device).cuda_stream
     launch(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-        dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-        dv.data_ptr(), delta.data_ptr(), B, Hq, Hkv, T, _bth(q), _bth(k),
+        dout.data_ptr(), lse.data_ptr(), *(t.data_ptr() for t in doc),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(),
+        B, Hq, Hkv, T, _bth(q), _bth(k),
         _bth(v), _bth(out), _bth(dout), _bth(dq), _bth(dk), _bth(dv), T,
         float(scale), s)
     return dq, dk, dv
 
 
 def gqa_backward(q, k, v, out, lse, dout, scale=None, dq=None, dk=None,
-                 dv=None, delta=None):
+                 dv=None, delta=None, doc_start=None, doc_end=None):
     """dq (B, Hq, T, 64) and dk, dv (B, Hkv, T, 64) of ``gqa_forward`` on the
     current stream, as views of contiguous (B, T, H, 64) bf16 buffers.  A
     dout the kernel cannot read in place (a stride rule) is made contiguous
     once; anything else outside ``can_use_backward`` raises.  ``dq``/``dk``/
     ``dv`` (views to write into) and the fp32 (B, Hq, T) workspace ``delta``
-    may be passed in (tests put guard regions around them)."""
+    may be passed in (tests put guard regions around them).  With
+    ``doc_start`` and ``doc_end`` (both or neither) it is the document-masked
+    backward of ``gqa_forward(..., doc_start=doc_start)``."""
+    if doc_start is not None or doc_end is not None:
+        return _backward(HEAD_DIM, _core.gqa_attn_bwd_doc_hd64, q, k, v, out,
+                         lse, dout, scale, dq, dk, dv, delta,
+                         (doc_start, doc_end))
     return _backward(HEAD_DIM, _core.gqa_attn_bwd_causal_hd64, q, k, v, out,
                      lse, dout, scale, dq, dk, dv, delta)
 
@@ -194,6 +261,28 @@ class _FusedCausalGqaAttn(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         dq, dk, dv = gqa_backward(q, k, v, out, lse, dout, ctx.scale)
         return dq, dk, dv, None
+
+
+class _FusedDocGqaAttn(torch.autograd.Function):
+    """The document-masked kernels, head dim 64."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, doc_start, doc_end):
+        if not can_use(q, k, v, doc_start, doc_end):
+            raise ValueError("fused_gqa_attn: inputs the document-masked "
+                             "kernels do not take (see can_use)")
+        out, lse = gqa_forward(q, k, v, scale, doc_start=doc_start)
+        out = out.transpose(1, 2)
+        ctx.save_for_backward(q, k, v, out, lse, doc_start, doc_end)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, doc_start, doc_end = ctx.saved_tensors
+        dq, dk, dv = gqa_backward(q, k, v, out, lse, dout, ctx.scale,
+                                  doc_start=doc_start, doc_end=doc_end)
+        return dq, dk, dv, None, None, None
 
 
 class _FusedCausalGqaAttnHd128(torch.autograd.Function):
@@ -235,16 +324,26 @@ class _FusedCausalGqaAttnHd128Own(_FusedCausalGqaAttnHd128):
 
 
 def fused_causal_gqa_attention(q, k, v, scale=None, *,
-                               own_backward_hd128=False):
+                               own_backward_hd128=False, doc_ids=None,
+                               doc_bounds=None):
     """softmax(scale * q k^T + causal mask) v with grouped kv heads, for bf16
     q (B, Hq, T, D) and k, v (B, Hkv, T, D) views, D 64 or 128; returns
     (B, Hq, T, D) over a contiguous (B, T, Hq, D) buffer.  The backward is
     ``gqa_backward`` at D = 64; at D = 128 it is the aten efficient-attention
     backward on expanded K/V, or ``gqa_backward_hd128`` with
     ``own_backward_hd128=True`` (which D = 64 ignores).  Inputs outside
-    ``can_use`` raise."""
+    ``can_use`` raise.
+
+    ``doc_ids`` (B, T), equal values in contiguous runs, adds the document
+    mask of a packed batch: key j counts for query i only if both lie in one
+    document.  D = 64 only.  A caller with many layers passes
+    ``doc_bounds=doc_start_end(doc_ids)`` instead, built once."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if doc_ids is not None or doc_bounds is not None:
+        if doc_bounds is None:
+            doc_bounds = doc_start_end(doc_ids)
+        return _FusedDocGqaAttn.apply(q, k, v, float(scale), *doc_bounds)
     if torch.is_tensor(q) and q.dim() == 4 and q.shape[-1] == 128:
         fn = (_FusedCausalGqaAttnHd128Own if own_backward_hd128
               else _FusedCausalGqaAttnHd128)
